@@ -1,6 +1,7 @@
 """Headline benchmark: decode tokens/sec + vision-prefill images/sec, Qwen2-VL-2B bf16 (BASELINE.json).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload qwen2vl-2b | nanollava | qwen2vl-7b-b32 | qwen2vl-2b-w4]
+                    [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -118,10 +119,19 @@ def main():
     ap.add_argument("--dry-run", action="store_true",
                     help="CPU rehearsal of the multi-rank path: launcher, rendezvous (gloo), weight-arena broadcast, request deal, "
                          "timing protocol, result gather, JSON line - no kernels (tests/test_host_cpu.py runs it with --gpus 2)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned (rank 0's greedy tokens) as "
+                         "DIR/tokens.npy (float64): the inputs are seeded, so two builds can be compared output for output")
     args = ap.parse_args()
 
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    if args.dump_outputs:
+        if args.workload != "qwen2vl-2b" or args.dry_run:
+            ap.error("--dump-outputs: the default workload (qwen2vl-2b) only")
+        args.dump_outputs = os.path.abspath(args.dump_outputs)          # the stage children may run from another directory
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # `python bench.py --gpus N` outside torchrun: launch the N ranks ourselves (one process per GPU over RCCL, the form
         # the driver uses: python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...)
@@ -193,6 +203,8 @@ def _child(args, stage, timeout_s):
 
     cmd = [sys.executable, os.path.abspath(__file__), "--stage", stage, "--gpus", "1", "--steps", str(args.steps), "--warmup", str(args.warmup),
            "--max-tokens", str(args.max_tokens), "--lookahead", str(args.lookahead), "--vit-batch", str(args.vit_batch)]
+    if stage == "headline" and getattr(args, "dump_outputs", ""):
+        cmd += ["--dump-outputs", args.dump_outputs]
     try:
         r = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout_s)
         rc, so, se = r.returncode, r.stdout, r.stderr

@@ -49,6 +49,11 @@ def stage_headline(args, rank, ws, local):
     torch.cuda.synchronize()
     parallel.barrier()
     wall = parallel.max_over_ranks(time.perf_counter() - t0, dev)
+    if getattr(args, "dump_outputs", "") and rank == 0:
+        # what generate_step handed the caller in the last timed step (return_logprobs=False: the tokens alone); float64
+        # holds every token id exactly
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "tokens.npy"), np.asarray(toks, dtype=np.float64))
     dec_max = parallel.max_over_ranks(dec_s, dev)
     pre_max = parallel.max_over_ranks(pre_s, dev)
     prep_max = parallel.max_over_ranks(host_prep_s, dev)

@@ -46,12 +46,20 @@ def test_driver_command_default_line():
 
 
 @pytest.mark.parametrize("layout", ["identity", "paged"])
-def test_headline_configuration_under_both_kv_layouts(layout):
+def test_headline_configuration_under_both_kv_layouts(layout, tmp_path):
     """The benchmark's engine (2B dims, kv_pool_tokens=32768, max_seqs=40: a 37 GB identity pool or the shared free list), a 448 x
-    448 image + 128 text tokens, 256 greedy tokens, lookahead 8 - the configuration no other test builds."""
-    out, _ = _run(["--stage", "headline", "--steps", "1", "--warmup", "1"], env={"VLM_KV_LAYOUT": layout})
+    448 image + 128 text tokens, 256 greedy tokens, lookahead 8 - the configuration no other test builds.  --dump-outputs writes
+    the last timed step's tokens."""
+    import numpy as np
+
+    out, _ = _run(["--stage", "headline", "--steps", "1", "--warmup", "1", "--dump-outputs", str(tmp_path / "dump")],
+                  env={"VLM_KV_LAYOUT": layout})
     assert out["config"]["max_tokens"] == 256 and out["config"]["decode_lookahead"] == 8 and out["config"]["prompt_tokens"] == 386
     assert out["value"] > 100.0 and 0.05 < out["roofline"]["frac"] < 1.0
+    assert out["steps"] == 1 and out["ms_per_step"] > 0.0
+    toks = np.load(tmp_path / "dump" / "tokens.npy")
+    assert toks.dtype == np.float64 and toks.shape == (256,)
+    assert np.array_equal(toks, np.round(toks)) and toks.min() >= 0 and toks.max() < 151936
 
 
 def test_headline_canary_with_one_hipmalloc_per_tensor():

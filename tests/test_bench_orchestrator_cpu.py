@@ -106,3 +106,28 @@ def test_clock_sampler_reads_the_starred_level_and_degrades_without_sysfs(tmp_pa
     with d:
         pass
     assert "before" in d.summary() and "after" in d.summary()
+
+
+def test_dump_outputs_and_steps_arguments(monkeypatch, tmp_path):
+    """--dump-outputs reaches the headline child (an absolute path) and no other; --steps 0 and a dump of another workload
+    are refused before anything runs."""
+    import subprocess
+
+    import bench
+
+    cmds = []
+
+    def fake_run(cmd, **kw):
+        cmds.append(cmd)
+        return subprocess.CompletedProcess(cmd, 0, stdout=json.dumps(HEAD) + "\n", stderr="")
+
+    monkeypatch.setattr(subprocess, "run", fake_run)
+    dump = str(tmp_path / "dump")
+    bench._child(_args(dump_outputs=dump), "headline", 10)
+    bench._child(_args(dump_outputs=dump), "extras", 10)
+    assert cmds[0][cmds[0].index("--dump-outputs") + 1] == dump and "--dump-outputs" not in cmds[1]
+    monkeypatch.undo()
+    for extra in (["--steps", "0"], ["--dump-outputs", dump, "--workload", "nanollava"], ["--dump-outputs", dump, "--dry-run"]):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + extra, capture_output=True, text=True, timeout=120)
+        assert r.returncode == 2 and "error:" in r.stderr, (extra, r.stderr[-500:])
+    assert not os.path.exists(dump)
