@@ -1,7 +1,7 @@
 """Headline benchmark: decode tokens/sec + vision-prefill images/sec, Qwen2-VL-2B bf16 (BASELINE.json).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload qwen2vl-2b | nanollava | qwen2vl-7b-b32 | qwen2vl-2b-w4]
-                    [--dump-outputs DIR]
+                    [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -15,6 +15,11 @@ ViT prefill -> projector -> LLM prefill -> 256 greedy tokens (EOS disabled), bat
 per GPU.  N > 1: one process per GPU (RCCL), weights broadcast from rank 0 at load,
 every rank serves its own request stream (weak scaling, no collective in the step).
 Rank 0 prints ONE JSON line; `value` = whole-job decode tokens/s.
+
+A plain run measures the headline figure alone: set-up, W warm-up steps, K timed steps, --dump-outputs, the line.  `--full`
+adds everything else the line can carry - per-kernel rooflines, ViT throughput, batched / wide / continuous / sampled decode,
+the CPU baselines, the short runs of the other BASELINE configs, GPU clocks (the default workload on one GPU runs each part in
+a process of its own: `orchestrate`); `--no-extras`, `--no-cpu-baseline`, `--no-cpu-hf` and `--no-configs` narrow a --full run.
 """
 
 from __future__ import annotations
@@ -106,16 +111,19 @@ def main():
     ap.add_argument("--lookahead", type=int, default=8)
     ap.add_argument("--vit-batch", type=int, default=64,
                     help="336x336 images per vision-tower call of the ViT throughput line (16 = the workload of rounds 1-4 is reported "
-                         "next to it; 68 images, where every GEMM fills its last round of 256 workgroups, measured +0.4 %: the tail of a "
+                         "next to it; 68 images, where every GEMM fills its last round of 256 workgroups, measured +0.4 %%: the tail of a "
                          "launch is not a whole round)")
     ap.add_argument("--workload", default="qwen2vl-2b", choices=["qwen2vl-2b", "nanollava", "qwen2vl-7b-b32", "qwen2vl-2b-w4", "phi35v-w4-b16", "idefics2-b8"])
     ap.add_argument("--kv-bits", type=int, default=0, help="phi35v-w4-b16: 8 = uniform 8-bit KV cache (kv_bits of the reference)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-cpu-hf", action="store_true", help="skip the HuggingFace torch-CPU second opinion of cpu_baseline")
-    ap.add_argument("--no-extras", action="store_true", help="skip kernel rooflines / ViT throughput (profiling runs)")
-    ap.add_argument("--no-configs", action="store_true", help="skip the short runs of the other BASELINE configs in the default line")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: the extras, the CPU baselines and the other configs (off: the "
+                         "timed steps alone)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baselines")
+    ap.add_argument("--no-cpu-hf", action="store_true", help="--full without the HuggingFace torch-CPU second opinion of cpu_baseline")
+    ap.add_argument("--no-extras", action="store_true", help="--full without kernel rooflines / ViT throughput / the other decode forms")
+    ap.add_argument("--no-configs", action="store_true", help="--full without the short runs of the other BASELINE configs in the default line")
     ap.add_argument("--stage", default="", choices=["", "headline", "extras"],
-                    help="internal: one stage of the default single-GPU line in a process of its own (see orchestrate)")
+                    help="internal: one stage of the --full single-GPU line in a process of its own (see orchestrate)")
     ap.add_argument("--dry-run", action="store_true",
                     help="CPU rehearsal of the multi-rank path: launcher, rendezvous (gloo), weight-arena broadcast, request deal, "
                          "timing protocol, result gather, JSON line - no kernels (tests/test_host_cpu.py runs it with --gpus 2)")
@@ -123,6 +131,8 @@ def main():
                     help="after the timed steps, write what the last timed step returned (rank 0's greedy tokens) as "
                          "DIR/tokens.npy (float64): the inputs are seeded, so two builds can be compared output for output")
     args = ap.parse_args()
+    if not args.full:           # a plain run: nothing beyond the headline figure, in every workload
+        args.no_extras = args.no_cpu_baseline = args.no_configs = True
 
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
@@ -181,21 +191,22 @@ def main():
         parallel.shutdown()
         return
     args.max_tokens = args.max_tokens or 256
-    if args.stage == "headline" or ws > 1:
-        # one rank of the N-rank job (torchrun / the self-launch above), or the headline child of the single-GPU orchestrator
-        rank, ws, local = parallel.init()
-        out = stage_headline(args, rank, ws, local)
-        if rank == 0:
-            if not args.stage:
-                out.pop("_traffic_gate_up", None)          # (the orchestrator's hand-over field)
-            print(json.dumps(out), flush=True)
-        parallel.barrier()
-        parallel.shutdown()
-        return
     if args.stage == "extras":
         print(json.dumps(stage_extras(args)), flush=True)
         return
-    orchestrate(args)
+    if args.full and ws == 1 and not args.stage:
+        orchestrate(args)
+        return
+    # the timed region in this process: a plain run, one rank of the N-rank job (torchrun / the self-launch above), or the
+    # headline child of the --full orchestrator
+    rank, ws, local = parallel.init()
+    out = stage_headline(args, rank, ws, local)
+    if rank == 0:
+        if not args.stage:
+            out.pop("_traffic_gate_up", None)          # (the orchestrator's hand-over field)
+        print(json.dumps(out), flush=True)
+    parallel.barrier()
+    parallel.shutdown()
 
 def _child(args, stage, timeout_s):
     """Run one stage of the default line as `bench.py --stage <stage>` -> (last JSON line or None, returncode, stderr tail)."""
@@ -223,7 +234,7 @@ def _child(args, stage, timeout_s):
     return doc, rc, se.strip()[-600:]
 
 def orchestrate(args):
-    """`python bench.py` on one GPU: this process never touches the GPU.  The headline (timed region) runs in a child whose JSON
+    """`python bench.py --full` on one GPU: this process never touches the GPU.  The headline (timed region) runs in a child whose JSON
     is echoed to stderr the moment it exists; the extras, the CPU baseline and the other configs follow, each in a process of
     its own, and ONE enriched line goes to stdout at the end.  A headline child killed by a signal is re-run (up to 3 attempts,
     every failed attempt is reported in `headline_attempts`)."""

@@ -3,7 +3,7 @@
 cd "$GRAFT_REPO_ROOT" || exit 1
 O=gpurun_out/r06_final; mkdir -p $O
 timeout 3000 python3 -m pytest tests -q -m gpu -x > $O/pytest.out 2>&1; echo "pytest rc=$?" >> $O/rc.txt
-timeout 1500 python3 bench.py --gpus 1 --steps 3 --warmup 1 > $O/bench.json 2> $O/bench.err; echo "bench rc=$?" >> $O/rc.txt
+timeout 1500 python3 bench.py --gpus 1 --full --steps 3 --warmup 1 > $O/bench.json 2> $O/bench.err; echo "bench rc=$?" >> $O/rc.txt
 cat $O/rc.txt; tail -4 $O/pytest.out; python3 - <<'PY'
 import json
 d=json.load(open("gpurun_out/r06_final/bench.json"))

@@ -23,10 +23,28 @@ def _run(extra, env=None, timeout=900):
     return json.loads(lines[0]), r.stderr
 
 
+def test_plain_run_is_the_headline_alone():
+    """`python bench.py --gpus 1 --steps 1 --warmup 1`: the timed region in the process itself and nothing else - no extras, CPU
+    baselines, other configs or clock samples in the line, and at most 30 s of the whole run spent outside the steps."""
+    import time
+
+    t0 = time.perf_counter()
+    out, err = _run(["--steps", "1", "--warmup", "1"])
+    outside_s = time.perf_counter() - t0 - (out["steps"] + out["warmup"]) * out["ms_per_step"] * 1e-3
+    assert out["metric"].startswith("decode tokens/sec") and out["unit"] == "tokens/s" and out["n_gpus"] == 1
+    assert out["steps"] == 1 and out["warmup"] == 1 and out["value"] > 100.0 and out["dtype"] == "bf16"
+    assert out["higher_is_better"] is True and out["ms_per_step"] > 0.0 and 0.05 < out["roofline"]["frac"] < 1.0
+    for k in ("kernel_rooflines", "roofline_kernel", "roofline_vit", "batch8_decode", "sampled_decode", "cpu_baseline", "configs",
+              "gpu_clocks", "headline_attempts", "_traffic_gate_up"):
+        assert k not in out, k
+    assert "vit" not in out["roofline"] and "[bench] headline: {" not in err
+    assert outside_s < 30.0, outside_s
+
+
 def test_driver_command_default_line():
-    """`python bench.py --gpus 1 --steps 2 --warmup 1` through the orchestrator: headline child + extras child; the line carries
-    the roofline objects and no stage failed."""
-    out, err = _run(["--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-configs"])
+    """`python bench.py --gpus 1 --full --steps 2 --warmup 1` through the orchestrator: headline child + extras child; the line
+    carries the roofline objects and no stage failed."""
+    out, err = _run(["--full", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-configs"])
     assert out["metric"].startswith("decode tokens/sec") and out["unit"] == "tokens/s" and out["n_gpus"] == 1
     assert out["steps"] == 2 and out["warmup"] == 1 and out["value"] > 100.0
     assert "headline_attempts" not in out, out.get("headline_attempts")          # ANY retry of the headline child fails the suite

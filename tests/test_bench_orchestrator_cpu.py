@@ -131,3 +131,43 @@ def test_dump_outputs_and_steps_arguments(monkeypatch, tmp_path):
         r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + extra, capture_output=True, text=True, timeout=120)
         assert r.returncode == 2 and "error:" in r.stderr, (extra, r.stderr[-500:])
     assert not os.path.exists(dump)
+
+
+def test_plain_run_times_the_headline_in_process_and_full_runs_the_orchestrator(monkeypatch, capsys):
+    """`bench.py --gpus 1 --steps K --warmup W` runs the timed region in its own process and prints its line with nothing else
+    started (no child, no extras, no CPU baseline, no other configs); `--full` hands the same arguments to the orchestrator,
+    whose --no-* options still narrow it."""
+    import bench
+
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
+        monkeypatch.delenv(k, raising=False)
+    seen = []
+
+    def fake_headline(args, rank, ws, local):
+        seen.append(("headline", args))
+        return dict(HEAD)
+
+    def refuse(*a, **kw):
+        raise AssertionError("a plain run started more than its timed region")
+
+    monkeypatch.setattr(bench, "stage_headline", fake_headline)
+    monkeypatch.setattr(bench, "orchestrate", lambda args: seen.append(("orchestrate", args)))
+    for name in ("_child", "stage_extras", "cpu_baseline", "other_configs"):
+        monkeypatch.setattr(bench, name, refuse)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "4", "--warmup", "2"])
+    bench.main()
+    lines = [ln for ln in capsys.readouterr().out.strip().splitlines() if ln.startswith("{")]
+    assert len(lines) == 1 and [s[0] for s in seen] == ["headline"]
+    d = json.loads(lines[0])
+    assert d["value"] == 1100.0 and "_traffic_gate_up" not in d
+    a = seen[0][1]
+    assert (a.steps, a.warmup, a.max_tokens, a.full) == (4, 2, 256, False)
+    assert a.no_extras and a.no_cpu_baseline and a.no_configs
+
+    seen.clear()
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "4", "--warmup", "2", "--full", "--no-configs"])
+    bench.main()
+    assert [s[0] for s in seen] == ["orchestrate"] and capsys.readouterr().out == ""
+    a = seen[0][1]
+    assert (a.steps, a.warmup, a.max_tokens, a.full) == (4, 2, 256, True)
+    assert not a.no_extras and not a.no_cpu_baseline and a.no_configs
