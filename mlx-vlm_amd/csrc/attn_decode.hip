@@ -629,10 +629,13 @@ __global__ __launch_bounds__(64) void attn_decode_pagesplit_q8_kernel(
         ls += pr;
         const u32x4_t w4 = vq[t][r >> 1];
         const unsigned w0 = (r & 1) ? w4[2] : w4[0], w1 = (r & 1) ? w4[3] : w4[1];
-        pp[0][r] = ok ? pr * bf_lo(w0) : 0.f;
-        pp[1][r] = ok ? pr * bf_lo(w1) : 0.f;
-        pbias[0] += ok ? pr * (bf_hi(w0) - 1024.f * bf_lo(w0)) : 0.f;         // the V operands are 1024 + n as well
-        pbias[1] += ok ? pr * (bf_hi(w1) - 1024.f * bf_lo(w1)) : 0.f;
+        // the V operands are 1024 + n as well: the constant leaves through the SAME fp16 value p * scale the MFMA takes, so
+        // its rounding error multiplies n, not 1024 + n (taking 1024 * p * scale out in fp32 left 2^-11 * 1024 * p * scale
+        // per key in O: 4.2e-3 .. 4.6e-3 rel-rms from the exact result instead of the 2.3e-3 of P's own bf16 rounding)
+        pp[0][r] = ok ? (float)(_Float16)(pr * bf_lo(w0)) : 0.f;
+        pp[1][r] = ok ? (float)(_Float16)(pr * bf_lo(w1)) : 0.f;
+        pbias[0] += ok ? pr * bf_hi(w0) - 1024.f * pp[0][r] : 0.f;          // (an unwritten slot's bias word may be NaN)
+        pbias[1] += ok ? pr * bf_hi(w1) - 1024.f * pp[1][r] : 0.f;
       }
       // k-slot 8 gq + j of step u <- tile 2u (j < 4) / tile 2u + 1 (j >= 4): tile t fills words (t & 1) * 2, + 1 of step t >> 1
 #pragma unroll

@@ -17,10 +17,10 @@ import pytest
 import torch
 
 from oracle import ops as O
+from tests import attn_exact as A
 
 pytestmark = pytest.mark.gpu
 BF, F64 = torch.bfloat16, torch.float64
-VSLOT = [(w & 32) + 8 * (((w & 31) & 15) >> 2) + 4 * ((w & 31) >> 4) + (w & 3) for w in range(64)]
 T, D, I, Hq, Hkv, hd = 64, 1536, 8960, 12, 2, 128
 
 
@@ -112,18 +112,9 @@ def test_vision_tower_flash_attention_against_the_exactly_rounded_result(vops):
 
 
 def _paged(n, seed):
-    max_pages = (n + 63) // 64 + 1
-    kpool = torch.full((max_pages, Hkv, hd // 8, 64, 8), float("nan"), dtype=BF)      # unwritten slots hold NaN on purpose
-    vpool = torch.full((max_pages, Hkv, hd, 64), float("nan"), dtype=BF)
     q, k, v = rnd(1, Hq * hd, seed=seed), rnd(n, Hkv, hd, seed=seed + 1), rnd(n, Hkv, hd, seed=seed + 2)
-    for p in range((n + 63) // 64):
-        m = min(64, n - p * 64)
-        kpool[p, :, :, :m, :] = k[p * 64:p * 64 + m].permute(1, 0, 2).reshape(Hkv, m, hd // 8, 8).permute(0, 2, 1, 3)
-        vpool[p][:, :, VSLOT[:m]] = v[p * 64:p * 64 + m].permute(1, 2, 0)
-    rep = Hq // Hkv
-    qq = q.view(Hq, 1, hd).to(F64)
-    kk, vv = k.permute(1, 0, 2).to(F64).repeat_interleave(rep, 0), v.permute(1, 0, 2).to(F64).repeat_interleave(rep, 0)
-    exact = (torch.softmax(qq @ kk.transpose(-1, -2) * hd ** -0.5, -1) @ vv).to(BF).reshape(1, Hq * hd)
+    _, kpool, vpool, max_pages = A.build_pools([k], [v], seed=seed, identity=True)      # unwritten slots hold NaN on purpose
+    exact = A.decode_exact(q, [k], [v], hd ** -0.5)
     orc = O.sdpa(q.view(1, Hq, 1, hd), k.permute(1, 0, 2)[None], v.permute(1, 0, 2)[None], hd ** -0.5)[0, :, 0].reshape(1, Hq * hd)
     return q, kpool, vpool, max_pages, exact, orc
 

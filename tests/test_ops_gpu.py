@@ -3,8 +3,9 @@ against the oracle (oracle/ops.py) on the same seeded bf16 inputs.
 
 Tolerances (stated per test): the HIP kernels and the oracle both accumulate in
 fp32 but in different orders, so bf16 outputs agree to ~1 ulp (<= 2^-7 relative)
-with a small absolute floor; attention additionally rounds P to bf16 for the
-MFMA (flash-attention convention), stated below.  Integer outputs (tokens,
+with a small absolute floor.  Attention is held to the oracle AND to the exactly
+rounded result (tests/attn_exact.py: P as hi + lo bf16 for decode and D = 128
+prefill, one bf16 P at D = 64 / 80 and in the 8-bit kernel).  Integer outputs (tokens,
 indices, copies) are bit-exact.
 """
 import math
@@ -15,10 +16,9 @@ import pytest
 import torch
 
 from oracle import ops as O
+from tests import attn_exact as A
+from tests.attn_exact import VSLOT
 from tests.helpers import bf16_close
-
-# V pool key-slot order inside a page (csrc/common.hpp vlm_vslot)
-VSLOT = [(w & 32) + 8 * (((w & 31) & 15) >> 2) + 4 * ((w & 31) >> 4) + (w & 3) for w in range(64)]
 
 
 def v_to_pool(v_tokens):
@@ -227,8 +227,8 @@ def _ref_attn_varlen(q, k, v, lens, scale, causal):
     (128, 2, 1, False, [130]),
 ])
 def test_attn_prefill(vops, D, Hq, Hkv, causal, lens):
-    """tolerance: P is rounded to bf16 before P.V (the oracle keeps P in fp32) -> relative 2^-8 noise
-    averaged over the keys: |err| <= 2 bf16 ulps of the output + 2% of the output rms."""
+    """against the oracle: 2 bf16 ulps + 2 % of the output rms; against the exactly rounded result: the bar class of the
+    P form (hi + lo at D = 128, one bf16 P at D = 64 / 80)."""
     T = sum(lens)
     q, k, v = rnd(T, Hq, D, seed=21), rnd(T, Hkv, D, seed=22), rnd(T, Hkv, D, seed=23)
     scale = D ** -0.5
@@ -239,6 +239,8 @@ def test_attn_prefill(vops, D, Hq, Hkv, causal, lens):
     out = vops.attn_prefill(qkv, qkv[:, Hq * D:], qkv[:, (Hq + Hkv) * D:], cu, nqb, Hq, Hkv, D, scale, causal)
     ok, rep = bf16_close(out.view(T, Hq, D), ref, ulps=2, atol_rms=2e-2)
     assert ok, rep
+    A.check(f"test_attn_prefill D={D} {Hq}/{Hkv} causal={causal} {lens}", out.view(T, Hq, D),
+            A.prefill_exact(q, k, v, lens, scale, causal, dev="cuda"), A.prefill_class(D), A.query_rows(lens)[1])
 
 
 @pytest.mark.parametrize("D,Hq,Hkv,causal,lens,starts", [
@@ -269,6 +271,9 @@ def test_attn_prefill_query_start_rows_before_it_are_keys_only(vops, D, Hq, Hkv,
     o = out.cpu().view(T, Hq, D)
     ok, rep = bf16_close(o[is_q], ref[is_q], ulps=2, atol_rms=2e-2)
     assert ok, rep
+    A.check(f"q_start prefill D={D} {Hq}/{Hkv} starts={starts}", o[is_q],
+            A.prefill_exact(q, k, v, lens, scale, causal, starts=starts, dev="cuda")[is_q], A.prefill_class(D),
+            A.query_rows(lens, starts)[1])
     assert bool((o[~is_q].float() == 7.0).all())
     with pytest.raises(Exception):                            # not together with the uniform-placement hint
         vops.attn_prefill(qkv, qkv[:, Hq * D:], qkv[:, (Hq + Hkv) * D:], cu, nqb, Hq, Hkv, D, scale, causal, out=out,
@@ -287,12 +292,14 @@ def test_attn_prefill_forced_rescale_spike(vops):
     out = vops.attn_prefill(qkv, qkv[:, H * D:], qkv[:, 2 * H * D:], cu, 4, H, H, D, D ** -0.5, False)
     ok, rep = bf16_close(out.view(T, H, D), ref, ulps=2, atol_rms=2e-2)
     assert ok, rep
+    A.check("forced rescale spike, D = 128", out.view(T, H, D), A.prefill_exact(q, k, v, [T], D ** -0.5, False, dev="cuda"), "hilo")
 
 
 @pytest.mark.parametrize("lens,nsplit", [([1, 130], 8), ([700, 64], 4), ([65], 1), ([2000, 1, 63, 64], 8),
                                          ([640], 1), ([513, 1100], 1), ([1, 64, 65, 2047], 1)])
 def test_attn_decode_paged(vops, lens, nsplit):
-    """P rounded to bf16 for the P.V MFMA (as in the prefill flash kernel): 2 ulps + 2% of the output rms."""
+    """P as hi + lo bf16 operands for the P.V MFMA: the oracle's 2 ulps + 2 % of the output rms, and the hi + lo class of the
+    exactly rounded result."""
     B, Hq, Hkv, D = len(lens), 12, 2, 128
     scale = D ** -0.5
     g = torch.Generator().manual_seed(27)
@@ -320,6 +327,10 @@ def test_attn_decode_paged(vops, lens, nsplit):
     out = vops.attn_decode_paged(q.cuda(), kpool.cuda(), vpool.cuda(), bt.cuda(), kv_len.cuda(), 0, Hq, Hkv, D, scale, nsplit)
     ok, rep = bf16_close(out, ref, ulps=2, atol_rms=2e-2)
     assert ok, rep
+    ks = [rnd(n, Hkv, D, seed=30 + b) for b, n in enumerate(lens)]
+    vs = [rnd(n, Hkv, D, seed=40 + b) for b, n in enumerate(lens)]
+    A.check(f"test_attn_decode_paged {lens} nsplit {nsplit}", out, A.decode_exact(q, ks, vs, scale, dev="cuda"), "hilo",
+            [(b, b + 1) for b in range(B)])
 
 
 @pytest.mark.parametrize("lens,nsplit,heads", [([1, 130], 8, (12, 2)), ([700, 64], 4, (12, 2)), ([65], 16, (12, 2)),
@@ -331,7 +342,8 @@ def test_attn_decode_paged_split_vs_oracle(vops, lens, nsplit, heads, identity):
     group) against the oracle's SDPA - lengths of 1 token, exact page multiples, more pages than splits (a workgroup
     walks several pages), more splits than pages (workgroups that only arrive), G = 1 / 4 / 6 / 7 / 8.  The launch is
     repeated on the same ticket words: a ticket that was not re-armed would make the second launch merge early or
-    never.  Same bar as the one-workgroup form: 2 ulps + 2 % of the output rms (P is rounded to bf16 for P.V)."""
+    never.  Same bars as the one-workgroup form: 2 ulps + 2 % of the output rms against the oracle, the hi + lo class
+    against the exactly rounded result."""
     Hq, Hkv = heads
     B, D = len(lens), 128
     scale = D ** -0.5
@@ -359,11 +371,15 @@ def test_attn_decode_paged_split_vs_oracle(vops, lens, nsplit, heads, identity):
     kv_len = torch.tensor(lens, dtype=torch.int32).cuda()
     tickets = torch.zeros(B * Hkv, dtype=torch.int32, device="cuda")
     qd, kd, vd, btd = q.cuda(), kpool.cuda(), vpool.cuda(), (None if identity else bt.cuda())
+    exact = A.decode_exact(q, [rnd(n, Hkv, D, seed=30 + b) for b, n in enumerate(lens)],
+                           [rnd(n, Hkv, D, seed=40 + b) for b, n in enumerate(lens)], scale, dev="cuda")
     for rep_i in range(3):
         out = vops.attn_decode_paged_split(qd, kd, vd, btd, kv_len, 0, Hq, Hkv, D, scale, nsplit, max_pages=max_pages,
                                            tickets=tickets)
         ok, rep = bf16_close(out, ref, ulps=2, atol_rms=2e-2)
         assert ok, (rep_i, rep)
+        A.check(f"page-split {lens} x{nsplit} {heads} identity={identity} launch {rep_i}", out, exact, "hilo",
+                [(b, b + 1) for b in range(B)])
         assert int(tickets.abs().sum()) == 0                      # re-armed
 
 
@@ -399,6 +415,8 @@ def test_attn_decode_partial_only_plus_oproj_prologue_merge(vops, n, nsplit, hea
     out = vops.gemv_attn_out_bf16_(po, pml, wo.cuda(), h.cuda().clone(), Hq, D)
     ok, rep = bf16_close(out, ref, ulps=3, atol_rms=2e-2)
     assert ok, rep
+    exact = A.oproj_exact(A.decode_exact(q, [k], [v], scale, dev="cuda"), wo, h, dev="cuda")
+    A.check(f"partials + o_proj prologue n={n} x{nsplit} {heads}", out, exact, "hilo")
 
 
 # ------------------------------------------------------------------ uniform 8-bit KV cache
@@ -472,7 +490,8 @@ def test_attn_decode_paged_q8_vs_oracle(vops, lens, nsplit, heads, identity):
     and attends over the 8-bit pools - against the oracle's quantized_scaled_dot_product_attention over its
     QuantizedKVCache (unwritten slots of the 8-bit pools hold garbage / NaN (scale, bias) words on purpose).  Launched
     twice (the second launch finds the token already quantised: same result).  2 ulps + 2 % of the rms, as the bf16
-    kernels; and the 8-bit pools end up bit-identical to a to_quantized of the whole sequence."""
+    kernels, and the q8 class of the exactly rounded result; the 8-bit pools end up bit-identical to a to_quantized of
+    the whole sequence."""
     from oracle import quant as Q
 
     Hq, Hkv = heads
@@ -500,6 +519,8 @@ def test_attn_decode_paged_q8_vs_oracle(vops, lens, nsplit, heads, identity):
                                         nsplit, quantize_new=True, max_pages=max_pages, tickets=tickets)
         ok, rep = bf16_close(out, ref, ulps=2, atol_rms=2e-2)
         assert ok, (rep_i, rep)
+        A.check(f"q8 decode {lens} x{nsplit} {heads} identity={identity} launch {rep_i}", out,
+                A.decode_q8_exact(q, ks, vs, scale, dev="cuda"), "q8", [(b, b + 1) for b in range(B)])
         assert int(tickets.abs().sum()) == 0
     k8b, v8b, ksbb, vsbb = _q8_empty(kpool)
     seq_all = torch.cat([torch.full((n,), b, dtype=torch.int32) for b, n in enumerate(lens)])
@@ -668,6 +689,10 @@ def test_attn_decode_partials_plus_gemv_attn_out(vops, lens, nsplit):
     out = vops.gemv_attn_out_(po, pml, wo.cuda(), hh, Hq, D)
     ok, rep = bf16_close(out, ref, ulps=2, atol_rms=1e-2)
     assert ok, rep
+    exact = A.decode_exact(q, [rnd(n, Hkv, D, seed=71 + b) for b, n in enumerate(lens)],
+                           [rnd(n, Hkv, D, seed=81 + b) for b, n in enumerate(lens)], scale, dev="cuda")
+    A.check(f"partials + gemv_attn_out {lens} x{nsplit}", out, A.oproj_exact(exact, wo, h, dev="cuda"), "hilo",
+            [(b, b + 1) for b in range(B)])
 
 
 @pytest.mark.parametrize("M,N,K", [(1024, 3840, 1280), (300, 640, 320), (77, 1280, 1216), (130, 1536, 8960)])
@@ -783,6 +808,8 @@ def test_attn_prefill_deferred_max_slow_ramp(vops, causal):
     out = vops.attn_prefill(qkv, qkv[:, H * D:], qkv[:, 2 * H * D:], cu, 5, H, H, D, D ** -0.5, causal)
     ok, rep = bf16_close(out.view(T, H, D), ref, ulps=2, atol_rms=2e-2)
     assert ok, rep
+    A.check(f"deferred-max slow ramp causal={causal}", out.view(T, H, D), A.prefill_exact(q, k, v, [T], D ** -0.5, causal, dev="cuda"),
+            "hilo")
 
 
 # ------------------------------------------------------------------ 256x256 phased GEMM (gemm256_bf16.hip)
