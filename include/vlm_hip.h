@@ -254,6 +254,22 @@ int vlm_attn_decode_paged_q8(const void* q, int ldq, const void* kpool16, const 
                              int kv_len_add, int B, int Hq, int Hkv, int D, float scale, int nsplit, void* part_o,
                              void* part_ml, void* tickets, void* out, int ldo, int quantize_new, void* stream);
 
+/* The same op at L > 1: a prompt CHUNK appended to a cache that is already 8-bit (QuantizedKVCache.update_and_fetch with an
+ * update of any length, cache.py:233-334, then quantized_scaled_dot_product_attention under the causal mask offset by the
+ * cache length, base.py:260-302 behind base.py:305-373).  Causal, varlen, GQA; keys and values are read straight from the
+ * 8-bit pools (the layouts above) through the block table - no vlm_kv_gather, no bf16 copy of the prefix.
+ * q / out: token-major bf16 rows of the chunk(s) only, head h of row t at ptr + t * ld + h * D; q is already rotated.
+ * Segment s = query rows cu_q[s] .. cu_q[s + 1] - 1 (int32 [nseg + 1]) of the sequence in block-table row seg_seq[s]
+ * (int32 [nseg]); its row r sits at absolute position q_start[s] + r (int32 [nseg]: tokens cached before the chunk) and sees
+ * slots 0 .. q_start[s] + r.  All of those must be 8-bit at the launch: the caller quantises the chunk's own tokens first
+ * (vlm_kv_quantize_tokens).  Later slots, stale bytes behind a trim and pages the table does not name never reach a result.
+ * total_qblocks = sum_s ceil(rows_s / 64) (host).  D == 128; arithmetic as vlm_attn_decode_paged_q8 (bf16(scale), q * scale
+ * and every score rounded to bf16, softmax in fp32, unnormalised probabilities rounded to bf16). */
+int vlm_attn_prefill_paged_q8(const void* q, int ldq, void* out, int ldo, const void* kpool8, const void* vpool8,
+                              const void* ksb, const void* vsb, const void* block_table, int max_pages, const void* seg_seq,
+                              const void* cu_q, const void* q_start, int nseg, int total_qblocks, int Hq, int Hkv, int D,
+                              float scale, void* stream);
+
 /* h[0][0:N] += merge(partials of vlm_attn_decode_paged_split's partial-only form) Wo^T for ONE decode row
  * (language.py:115-120,151): every thread of the o_proj GEMV loads one 8-element chunk of all nsplit <= 16 fp32 partials
  * and their (m, l) ahead of its weight stream and merges them in registers (bf16 Wo: the name).  Hq * D <= 2048. */

@@ -138,6 +138,8 @@ SIGNATURES = {
                                        c_void_p]),
     "vlm_attn_decode_paged_q8": (c_int, [c_void_p, c_int] + [c_void_p] * 7 + [c_int, c_void_p] + [c_int] * 5
                                  + [c_float, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
+    "vlm_attn_prefill_paged_q8": (c_int, [c_void_p, c_int, c_void_p, c_int] + [c_void_p] * 5 + [c_int] + [c_void_p] * 3
+                                  + [c_int] * 5 + [c_float, c_void_p]),
     "vlm_gemv_attn_out_bf16": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p] + [c_int] * 4 + [c_void_p]),
     "vlm_embed_gather": (c_int, [c_void_p] * 3 + [c_int] * 4 + [c_void_p]),
     "vlm_scatter_image_rows": (c_int, [c_void_p] * 3 + [c_int] * 4 + [c_void_p]),

@@ -358,6 +358,7 @@ class BatchGenerator:
     def _quantize_joined(self, seq):
         """the joined request's cached prompt becomes a QuantizedKVCache (engine hook: a mock engine has nothing to convert)"""
         self.lm.quantize_kv([seq], bits=int(self.kv_bits), group_size=64)
+        seq.q8_batch_policy = True      # (the batch step keeps the last layer of a deep stack bf16: vlm_kv_pool.q8_skip_last)
 
     def _row_logprobs(self, n: int) -> torch.Tensor:
         """log-prob of the token each of the first n rows has just sampled (f32 [n])"""

@@ -29,6 +29,7 @@
 
 #include "common.hpp"
 #include "attn_pagesplit.hpp"
+#include "attn_q8.hpp"
 #include "internal.h"
 #include "../../include/vlm_hip.h"
 
@@ -487,24 +488,7 @@ __global__ __launch_bounds__(256) void kv_quantize_tokens_kernel(const bf16_t* _
   sb[(page_head * PAGE + within) * 2 + j] = (unsigned)f2bf(pq.scale) | ((unsigned)f2bf(pq.bias) << 16);
 }
 
-typedef __attribute__((ext_vector_type(2))) unsigned int u32x2_t;
-typedef __attribute__((ext_vector_type(8))) _Float16 f16x8_t;
-// 8 u8 -> 8 fp16 values 1024 + n, ONE v_perm_b32 per two elements: byte n under the constant byte 0x64 is the half-precision
-// number 0x64nn = 1024 + n exactly (10 mantissa bits).  The constant 1024 is taken out again in the affine forms below
-// (scale * (q . (1024 + n)) + (bias - 1024 scale) * sum(q)), so no subtraction is spent per element - the u8 -> operand
-// conversion costs 4 VALU instructions per 8 elements instead of 12 (v_cvt_f32_ubyte + v_cvt_pk_bf16_f32).
-__device__ __forceinline__ f16x8_t q8_frag(const u32x2_t w) {
-  const unsigned x = w[0], y = w[1], k = 0x64646464u;
-  const u32x4_t v = {__builtin_amdgcn_perm(k, x, 0x04010400u), __builtin_amdgcn_perm(k, x, 0x04030402u),
-                     __builtin_amdgcn_perm(k, y, 0x04010400u), __builtin_amdgcn_perm(k, y, 0x04030402u)};
-  return __builtin_bit_cast(f16x8_t, v);
-}
-__device__ __forceinline__ unsigned pack_h2(float lo, float hi) {      // two fp32 -> packed fp16x2 (round to nearest even)
-  typedef _Float16 h2_t_ __attribute__((ext_vector_type(2)));
-  const h2_t_ v = {(_Float16)lo, (_Float16)hi};
-  return __builtin_bit_cast(unsigned, v);
-}
-
+// (q8_frag / pack_h2, the u8 -> fp16 operand conversion: attn_q8.hpp, shared with the prompt-chunk kernel)
 // The page-split decode attention over the 8-bit pools.  Arithmetic = the reference's typed graph as far as a split /
 // flash formulation allows: q * scale is a typed multiply (rounded to bf16); a score is the fp32 sum over the two groups
 // of scale_j * (q . n) + bias_j * sum(q) - the EXACT affine form of quantized_matmul, the integers entering the fp16 MFMA
@@ -810,15 +794,7 @@ extern "C" int vlm_attn_decode_paged_q8(const void* q, int ldq, const void* kpoo
   if ((size_t)B * Hq * nsplit * HD * 4 >= ((size_t)1 << 31)) return VLM_ERR_SHAPE;
   const int G = Hq / Hkv;
   hipStream_t st = (hipStream_t)stream;
-  // `queries *= scale` (base.py:272) with a python float: MLX converts the weak scalar to the ARRAY's dtype first, so the
-  // typed multiply uses bf16(scale) (128 ** -0.5 -> 0.08837890625) - pinned by tests/golden/kvquant_ref.npz, where the
-  // reference's own function runs; round-to-nearest-even on the host
-  {
-    unsigned u;
-    memcpy(&u, &scale, 4);
-    u = (u + 0x7fffu + ((u >> 16) & 1u)) & 0xffff0000u;
-    memcpy(&scale, &u, 4);
-  }
+  scale = vlm_bf16_scale(scale);      // the typed `queries *= scale` multiplies by bf16(scale): attn_q8.hpp
   // half-page units once the (row, kv head) pairs alone give every SIMD its waves (Phi-3.5 at 16 rows: 512 pairs): the 64-key
   // form holds 209 registers (2 waves per SIMD); VLM_ATTN_Q8_HALF = 0 / 1 forces (A/B)
   static const int hp_env = [] { const char* e = getenv("VLM_ATTN_Q8_HALF"); return e ? atoi(e) : -1; }();

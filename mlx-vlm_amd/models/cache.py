@@ -182,6 +182,7 @@ class PagedSequence:
         self._layer_off: Optional[List[int]] = None
         self.released = False
         self.q8 = False          # True once the sequence's cache has become a QuantizedKVCache (LanguageModel.quantize_kv)
+        self.q8_batch_policy = False      # True: quantised by a BatchGenerator, whose steps keep the last layer of a deep stack bf16
         # max_kv_size (reference RotatingKVCache, cache.py:442-625): None = unbounded.  `held` = entries the pool holds for this
         # sequence (== offset until the window is full), `ring` = the non-sink slots in the age order of their tokens
         self.max_size: Optional[int] = None

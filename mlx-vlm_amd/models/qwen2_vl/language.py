@@ -523,9 +523,16 @@ class LanguageModel:
         hd, Hq, Hkv = self.head_dim, t.num_attention_heads, t.num_key_value_heads
         D, QKV = t.hidden_size, (Hq + 2 * Hkv) * self.head_dim
         seqs = [c[0]._seq for c in caches]
-        if any(getattr(s, "q8", False) for s in seqs):
-            raise NotImplementedError("a prompt chunk onto a QUANTIZED KV cache (kv_bits): only decode steps attend over the "
-                                      "8-bit pools; continue such a conversation without kv_bits or from a fresh cache")
+        # sequences whose cache is a QuantizedKVCache: the chunk's tokens are quantised layer by layer as they are written and the
+        # attention reads the 8-bit pools (vlm_attn_prefill_paged_q8) - QuantizedKVCache.update_and_fetch with an update of any
+        # length, then quantized_scaled_dot_product_attention under the offset causal mask (cache.py:233-334, base.py:260-302).
+        # A mix of 8-bit and bf16 sequences is refused as in decode_run
+        if len({bool(s.q8) for s in seqs}) > 1:
+            raise RuntimeError("a prompt chunk cannot mix sequences with and without a quantized KV cache")
+        q8 = bool(seqs[0].q8)
+        if q8 and any(getattr(s, "q8_batch_policy", False) for s in seqs):
+            raise NotImplementedError("a prompt chunk onto a sequence quantised under the BATCH policy (the last layer of a deep "
+                                      "stack stays bf16, models/cache.py:8-21): only its decode steps are built")
         offs = [int(s.offset) for s in seqs]
         for n, s in zip(lengths, seqs):
             s.reserve(s.offset + n + reserve_extra)
@@ -556,7 +563,16 @@ class LanguageModel:
         # a decode row over its sequence's pages with kv_len = cache length + its index + 1 (its K / V are in the pages by then:
         # mrope_kvwrite_ below) - no gather of the prefix at all, and the keys are split over workgroups as in a decode step
         # (one 64-row query block per head walking 16k keys took ~0.4 ms per layer; profiles/r06_long_prompt_prefill.txt).
+        # (8-bit sequences too: rows of vlm_attn_decode_paged_q8 over the 8-bit pages, the chunk's tokens quantised first.  One wave of
+        #  vlm_attn_prefill_paged_q8 walks all the keys of its 16 rows, the decode rows split them over workgroups: 46 against 156 us
+        #  at 32 rows onto 4096 tokens, profiles/q8_prefill_attn.txt)
         short = T <= 64 and os.environ.get("VLM_ONTO_CACHE_DECODE_ATTN") != "0"
+        if q8:
+            cu_new_d = _lib.h2d(np.concatenate([[0], np.cumsum(lengths)]).astype(np.int32), dev)
+            seg_seq_d = _lib.h2d(np.asarray([s.seq for s in seqs], dtype=np.int32), dev)
+            nqb8 = int(sum((n + ops.Q8_PREFILL_QBLOCK - 1) // ops.Q8_PREFILL_QBLOCK for n in lengths))
+            new_seq_c, new_slot_c = new_seq_d.contiguous(), new_slot_d.contiguous()
+            q8_start_d = _lib.h2d(np.asarray(offs, dtype=np.int32), dev)
         if short:
             row_seq = np.concatenate([np.full(n, s.seq, np.int64) for n, s in zip(lengths, seqs)])
             row_len = np.concatenate([o + 1 + np.arange(n) for o, n in zip(offs, lengths)]).astype(np.int32)
@@ -580,6 +596,21 @@ class LanguageModel:
             ops.mrope_kvwrite_(qkv, Hq, Hkv, hd, pos_d[0], pos_d[1], pos_d[2], inv_tab, int(sec[0]), int(sec[1]),
                                kv_seq=new_seq_d.contiguous(), kv_slot=new_slot_d.contiguous(), block_table=bt, kpool=kp, vpool=vp,
                                qk_scale=getattr(t, "rope_qk_scale", None))
+            if q8:
+                # QuantizedKVCache.update_and_fetch: this layer's new rows become 8-bit, then the chunk attends over the 8-bit
+                # pages of [cached tokens | itself] in place - no full-length buffer, no gather
+                k8, v8, ksb, vsb = pool.kpool8[i], pool.vpool8[i], pool.ksb[i], pool.vsb[i]
+                ops.kv_quantize_tokens(kp, vp, k8, v8, ksb, vsb, new_seq_c, new_slot_c, bt, Hkv, hd)
+                if short:
+                    attn = ops.attn_decode_paged_q8(qkv, kp, vp, k8, v8, ksb, vsb, bt_rows, row_len_d, 0, Hq, Hkv, hd, scale, dec_nsplit,
+                                                    quantize_new=False)
+                else:
+                    attn = ops.attn_prefill_paged_q8(qkv, k8, v8, ksb, vsb, bt, seg_seq_d, cu_new_d, q8_start_d, nqb8, Hq, Hkv, hd, scale)
+                h = ops.gemm(attn, w[f"{i}.wo"], res=h, epilogue=ops.EPI_RESIDUAL)
+                xn = ops.rmsnorm(h, w[f"{i}.ln2"], t.rms_norm_eps)
+                act = ops.gemm(xn, w[f"{i}.wgu"], epilogue=ops.EPI_SWIGLU)
+                h = ops.gemm(act, w[f"{i}.wdown"], res=h, epilogue=ops.EPI_RESIDUAL)
+                continue
             if short:
                 attn = ops.attn_decode_paged(qkv, kp, vp, bt_rows, row_len_d, 0, Hq, Hkv, hd, scale, dec_nsplit)
                 h = ops.gemm(attn, w[f"{i}.wo"], res=h, epilogue=ops.EPI_RESIDUAL)

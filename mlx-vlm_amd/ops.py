@@ -375,6 +375,31 @@ def attn_decode_paged_q8(q, kpool16, vpool16, kpool8, vpool8, ksb, vsb, block_ta
     return out
 
 
+Q8_PREFILL_QBLOCK = 64      # query rows per workgroup of vlm_attn_prefill_paged_q8
+
+
+def attn_prefill_paged_q8(q, kpool8, vpool8, ksb, vsb, block_table, seg_seq, cu_q, q_start, total_qblocks, Hq, Hkv, D, scale,
+                          out=None):
+    """causal attention of prompt chunk(s) over the 8-bit KV pools (quantized_scaled_dot_product_attention at L > 1).
+    q [T, *]: data_ptr at head 0 of row 0, stride(0) = the row stride; rows cu_q[s] .. cu_q[s + 1] - 1 belong to the sequence
+    in block-table row seg_seq[s] and sit at positions q_start[s] + r (all int32, device).  The chunk's own tokens must be
+    quantised already (kv_quantize_tokens).  total_qblocks = sum ceil(rows_s / Q8_PREFILL_QBLOCK).  -> bf16 [T, Hq * D]"""
+    _dev(q, kpool8, vpool8, ksb, vsb, block_table, seg_seq, cu_q, q_start)
+    T = q.shape[0]
+    nseg = seg_seq.numel()
+    if cu_q.numel() != nseg + 1 or q_start.numel() != nseg:
+        raise ValueError(f"attn_prefill_paged_q8: {nseg} segments need cu_q [{nseg + 1}] and q_start [{nseg}]")
+    for t in (block_table, seg_seq, cu_q, q_start):
+        if t.dtype != torch.int32 or not t.is_contiguous():
+            raise ValueError("attn_prefill_paged_q8: block_table / seg_seq / cu_q / q_start are contiguous int32 tensors")
+    if out is None:
+        out = torch.empty(T, Hq * D, dtype=torch.bfloat16, device=q.device)
+    check(_lib.lib().vlm_attn_prefill_paged_q8(_p(q), q.stride(0), _p(out), out.stride(0), _p(kpool8), _p(vpool8), _p(ksb), _p(vsb),
+                                               _p(block_table), block_table.shape[1], _p(seg_seq), _p(cu_q), _p(q_start), nseg,
+                                               int(total_qblocks), Hq, Hkv, D, scale, _stream()), "attn_prefill_q8")
+    return out
+
+
 def embed_gather(ids, table, out=None):
     _dev(ids, table)
     T = ids.numel()
