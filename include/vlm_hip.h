@@ -463,7 +463,8 @@ typedef struct vlm_prefill_args {
 
 /* one decode step for B sequences (B in {1,2,4,8}); every buffer is device resident so the
  * step can be replayed from a graph: tok int32 [B] (in: token to feed, out: sampled token),
- * pos / ctx int32 [B] (rope position / keys in cache, advanced by the step), step int32 [1]. */
+ * pos / ctx int32 [B] (rope position / keys in cache, advanced by the step; int32 [2][B] under
+ * VLM_DECODE_WINDOW, see the flag), step int32 [1]. */
 typedef struct vlm_decode_args {
   int B;
   void *tok, *pos, *ctx, *step;
@@ -488,6 +489,17 @@ typedef struct vlm_decode_args {
 #define VLM_DECODE_ACT16 2      /* `act` holds 16 x intermediate_size elements (not B x): a step of 5..16 rows over bf16 weights
                                    may then hand the SwiGLU output to the down projection in the tiled layout of
                                    VLM_EPI_Y_TILED / VLM_EPI_X_TILED (rows padded to the MFMA tile's 16).  ABI v8. */
+#define VLM_DECODE_WINDOW 4     /* max_kv_size on the device (RotatingKVCache, models/cache.py:442-625): the rows' caches are rings
+                                   of VLM_MODE_WINDOW_SIZE slots whose first VLM_MODE_WINDOW_KEEP are never overwritten.  ctx and
+                                   pos then point at int32 [2][B]: ctx row 0 = n (entries held before the step's write), row 1 = w
+                                   (the slot the step writes); pos row 0 = p (rope position of the step), row 1 = d (the row's
+                                   rope delta).  The step writes K / V at slot w, attends over n + 1 entries (the rotation is
+                                   baked into the keys: slot order does not matter) and its tail advances
+                                     n' = min(n + 1, M - 1),  w' = w + 1 == M ? K : w + 1,
+                                     p' = VLM_MODE_WINDOW_RING_POS ? (r >= M ? K : r) + 1 + d  with r = p - d  :  p + 1.
+                                   B in {1, 2, 4, 8}, bf16 pools (8-bit pools: argument error), one rope table
+                                   (vlm_llm_config.rope_long_from > 0: argument error - that epilogue reads ctx as the offset).
+                                   A bit added within ABI v8: callers that pass [B] arrays never set it. */
 
 int vlm_llm_create(const vlm_llm_config* cfg, void** handle);          /* (host) */
 int vlm_llm_destroy(void* handle);
@@ -520,6 +532,15 @@ int vlm_llm_decode_launches(void* handle);
 #define VLM_TUNE_ATTN_MERGE 9       /* where the page-split attention of a ONE-row step is merged: 1 (default) = in the o_proj
                                        GEMV's prologue (partial-only attention launch, vlm_gemv_attn_out_bf16; needs bf16 Wo,
                                        Hq * D <= 2048, <= 16 splits), 0 = by the attention launch's last-arriving workgroup */
+/* Modes of the decode step: these keys DO change what a step computes (the sentence above holds for keys 6..9 only).  They
+ * travel through vlm_llm_set_tuning / vlm_llm_get_tuning because the C ABI is frozen at v8; changing a value drops the cached
+ * graphs of the handle as the tuning keys do.  Read by steps whose flags carry VLM_DECODE_WINDOW. */
+#define VLM_MODE_WINDOW_SIZE 16     /* M = max_kv_size: slots of a row's ring; 0 (default) = no window (the flag is then refused).
+                                       A window step needs M > keep + 1 */
+#define VLM_MODE_WINDOW_KEEP 17     /* K = the first K slots (attention sinks) are never overwritten (make_prompt_cache: 4) */
+#define VLM_MODE_WINDOW_RING_POS 18 /* 1: the rope position follows the ring's write index (the reference's Qwen2-VL reads
+                                       cache._idx as its offset, qwen2_vl/language.py:426-431); 0 (default): it follows the tokens
+                                       seen (cache.offset: the plain-rope families) */
 int vlm_llm_set_tuning(void* handle, int key, int value);
 int vlm_llm_get_tuning(void* handle, int key);
 

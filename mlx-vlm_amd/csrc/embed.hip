@@ -11,6 +11,7 @@
 //                         (reference mlx_vlm/models/cache.py:362) and pos = offset + rope_delta
 //                         (language.py:476-509) kept in device memory so a step can be graph-replayed
 #include "common.hpp"
+#include "internal.h"
 #include "../../include/vlm_hip.h"
 
 namespace {
@@ -53,12 +54,11 @@ __global__ __launch_bounds__(256) void cast_pad_kernel(const float* __restrict__
 }
 
 __global__ void decode_advance_kernel(int* __restrict__ ctx, int* __restrict__ pos, const int* __restrict__ tok,
-                                      int* __restrict__ out_ring, int ring_len, int* __restrict__ step, int B) {
+                                      int* __restrict__ out_ring, int ring_len, int* __restrict__ step, int B, VlmWindow wn) {
   const int b = threadIdx.x;
   const int s = *step;
   if (b < B) {
-    ctx[b] += 1;
-    pos[b] += 1;
+    vlm_window_advance(ctx, pos, B, b, wn);
     if (out_ring) out_ring[(size_t)(s % ring_len) * B + b] = tok[b];
   }
   __syncthreads();
@@ -103,12 +103,18 @@ extern "C" int vlm_cast_f32_bf16_pad(const void* src, void* dst, int rows, int c
   return VLM_OK;
 }
 
-extern "C" int vlm_decode_advance(void* ctx, void* pos, const void* tok, void* out_ring, int ring_len, void* step, int B,
-                                  void* stream) {
+VLM_INTERNAL int vlm_decode_advance_win(void* ctx, void* pos, const void* tok, void* out_ring, int ring_len, void* step, int B,
+                                        VlmWindow wn, void* stream) {
   if (!ctx || !pos || !tok || !step || B <= 0 || B > 256) return VLM_ERR_ARG;
   if (out_ring && ring_len <= 0) return VLM_ERR_ARG;
+  if (wn.M > 0 && (wn.K < 0 || wn.M <= wn.K + 1)) return VLM_ERR_ARG;
   hipLaunchKernelGGL(decode_advance_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (int*)ctx, (int*)pos,
-                     (const int*)tok, (int*)out_ring, ring_len, (int*)step, B);
+                     (const int*)tok, (int*)out_ring, ring_len, (int*)step, B, wn);
   VLM_CHECK_LAUNCH();
   return VLM_OK;
+}
+
+extern "C" int vlm_decode_advance(void* ctx, void* pos, const void* tok, void* out_ring, int ring_len, void* step, int B,
+                                  void* stream) {
+  return vlm_decode_advance_win(ctx, pos, tok, out_ring, ring_len, step, B, VlmWindow{0, 0, 0}, stream);
 }

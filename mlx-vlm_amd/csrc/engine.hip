@@ -35,6 +35,7 @@ struct DecodeGraph {
   vlm_penalty_args pen;                   // copy of *args.penalties (zeroed when there are none)
   vlm_decode_args args;
   vlm_kv_pool kv;
+  VlmWindow win;                          // the mode values a VLM_DECODE_WINDOW step was captured with (zero without the flag)
   hipGraph_t graph;
   hipGraphExec_t exec;
   int launches;
@@ -48,6 +49,8 @@ struct Tuning {
   int attn_pagesplit = 16;                // vlm_attn_decode_paged_split with up to this many workgroups per (row, kv head)
   int gemv_variant = 0;                   // A/B bits of the batch-1 GEMV launch shapes (VLM_TUNE_GEMV_VARIANT)
   int attn_merge = 1;                     // 1: one-row steps merge the page-split partials in the o_proj prologue
+  // modes of the decode step (VLM_MODE_*): unlike the knobs above these change what a VLM_DECODE_WINDOW step computes
+  int win_size = 0, win_keep = 0, win_ring_pos = 0;
 };
 
 struct Llm {
@@ -78,9 +81,14 @@ inline bool same_pen(const vlm_penalty_args& x, const vlm_penalty_args* y) {
          x.bias_val == y->bias_val && x.n_bias == y->n_bias && x.row_params == y->row_params && x.bias_stride == y->bias_stride;
 }
 
-inline bool same_key(const DecodeGraph& g, const vlm_decode_args& a, const vlm_kv_pool& kv) {
+// the window a step with these flags runs under ({0, 0, 0}: none)
+inline VlmWindow window_of(const Tuning& t, int flags) {
+  return (flags & VLM_DECODE_WINDOW) ? VlmWindow{t.win_size, t.win_keep, t.win_ring_pos} : VlmWindow{0, 0, 0};
+}
+
+inline bool same_key(const DecodeGraph& g, const vlm_decode_args& a, const vlm_kv_pool& kv, const VlmWindow& wn) {
   const vlm_decode_args& b = g.args;
-  return same_pen(g.pen, a.penalties) && a.B == b.B && a.tok == b.tok && a.pos == b.pos && a.ctx == b.ctx && a.step == b.step && a.h == b.h &&
+  return same_pen(g.pen, a.penalties) && wn.M == g.win.M && wn.K == g.win.K && wn.ring_pos == g.win.ring_pos && a.B == b.B && a.tok == b.tok && a.pos == b.pos && a.ctx == b.ctx && a.step == b.step && a.h == b.h &&
          a.qkv == b.qkv && a.attn == b.attn && a.act == b.act && a.logits == b.logits && a.logprobs == b.logprobs &&
          a.scratch == b.scratch && a.part_o == b.part_o && a.part_ml == b.part_ml && a.sample_ws == b.sample_ws &&
          a.out_ring == b.out_ring && a.ring_len == b.ring_len && a.nsplit == b.nsplit && a.temperature == b.temperature &&
@@ -156,6 +164,9 @@ extern "C" int vlm_llm_set_tuning(void* handle, int key, int value) {
     case VLM_TUNE_ATTN_PAGESPLIT: if (value < 0 || value > 32) return 1; slot = &m->tune.attn_pagesplit; break;
     case VLM_TUNE_GEMV_VARIANT: if (value < 0) return 1; slot = &m->tune.gemv_variant; break;
     case VLM_TUNE_ATTN_MERGE: if (value < 0 || value > 1) return 1; slot = &m->tune.attn_merge; break;
+    case VLM_MODE_WINDOW_SIZE: if (value < 0) return 1; slot = &m->tune.win_size; break;
+    case VLM_MODE_WINDOW_KEEP: if (value < 0) return 1; slot = &m->tune.win_keep; break;
+    case VLM_MODE_WINDOW_RING_POS: if (value < 0 || value > 1) return 1; slot = &m->tune.win_ring_pos; break;
     default: return 1;
   }
   if (key == VLM_TUNE_GEMV_VARIANT) vlm_gemv_set_variant(value);
@@ -175,6 +186,9 @@ extern "C" int vlm_llm_get_tuning(void* handle, int key) {
     case VLM_TUNE_ATTN_PAGESPLIT: return m->tune.attn_pagesplit;
     case VLM_TUNE_GEMV_VARIANT: return m->tune.gemv_variant;
     case VLM_TUNE_ATTN_MERGE: return m->tune.attn_merge;
+    case VLM_MODE_WINDOW_SIZE: return m->tune.win_size;
+    case VLM_MODE_WINDOW_KEEP: return m->tune.win_keep;
+    case VLM_MODE_WINDOW_RING_POS: return m->tune.win_ring_pos;
     default: return -1;
   }
 }
@@ -319,6 +333,16 @@ static int decode_impl(Llm* m, const vlm_decode_args* a, void* stream, int* laun
   const bool fused_sampled = fused_flag && a->temperature > 0.f;
   if ((a->flags & VLM_DECODE_FUSED_TAIL) && !fused_flag) return 1;   // the flag promises h == embed[tok] at entry
   const Tuning& tn = m->tune;
+  // VLM_DECODE_WINDOW (max_kv_size): ctx = [2][B] (n, w), pos = [2][B] (p, d).  The layer launches keep their signatures - the qkv
+  // epilogue writes at slot w = ctx + B and rotates by p = pos row 0, the attention runs over n + 1 = ctx row 0 + 1 entries - and
+  // the step's tail advances all four by the window rule (internal.h vlm_window_advance).  Not over the 8-bit pools (the
+  // reference: "RotatingKVCache Quantization NYI"), not with two rope tables (that epilogue reads the slot as the cache offset)
+  const VlmWindow wn = window_of(tn, a->flags);
+  if (a->flags & VLM_DECODE_WINDOW) {
+    if (wn.M <= wn.K + 1 || m->kv.kpool8 || c.rope_long_from > 0) return 1;
+    if (B != 1 && B != 2 && B != 4 && B != 8) return 1;
+  }
+  const void* const slot = (a->flags & VLM_DECODE_WINDOW) ? (const void*)((const int*)a->ctx + B) : (const void*)a->ctx;
   // WIDE steps (more than 16 rows): beyond one N tile of the skinny-M MFMA GEMM the projections run on the prefill GEMMs,
   // i.e. a layer is the prefill's launch sequence (vlm_llm_prefill above) with the paged decode attention in place of
   // the flash attention: RMSNorm -> qkv GEMM + bias -> M-RoPE + KV write at slot ctx[b] -> attention over the pages ->
@@ -354,22 +378,22 @@ static int decode_impl(Llm* m, const vlm_decode_args* a, void* stream, int* laun
       VlmGemmTail rt{};
       rt.kind = VLM_TAIL_ROPE_KV;
       rt.Hq = Hq; rt.Hkv = Hkv; rt.D = hd;
-      rt.pos = (const int*)a->pos; rt.inv_freq = (const float*)m->g.inv_freq; rt.slot = (const int*)a->ctx;
+      rt.pos = (const int*)a->pos; rt.inv_freq = (const float*)m->g.inv_freq; rt.slot = (const int*)slot;
       rt.block_table = (const int*)m->kv.block_table; rt.max_pages = m->kv.max_pages;
       rt.kpool = (unsigned short*)kp; rt.vpool = (unsigned short*)vp; rt.qk_scale = qk_scale; rt.long_from = c.rope_long_from;
       int done = 0;
       TRY(lin_gemm_tail(m, xn, w.wqkv, w.wqkv_sb, w.bqkv, nullptr, a->qkv, B, QKV, D, QKV, 0, w.bqkv ? VLM_EPI_BIAS : VLM_EPI_NONE,
                         &rt, &done, stream)); ++n;
       if (!done) {
-        TRY(vlm_mrope_kvwrite_decode(a->qkv, QKV, B, Hq, Hkv, hd, a->pos, m->g.inv_freq, c.mrope_sec0, c.mrope_sec1, a->ctx,
+        TRY(vlm_mrope_kvwrite_decode(a->qkv, QKV, B, Hq, Hkv, hd, a->pos, m->g.inv_freq, c.mrope_sec0, c.mrope_sec1, slot,
                                      m->kv.block_table, m->kv.max_pages, kp, vp, qk_scale, c.rope_long_from, stream)); ++n;
       }
     } else if (w.wqkv_sb) {
       TRY(vlm_gemv_w4_qkv_rope_kvwrite_ex(a->h, w.ln1_w, c.rms_eps, w.wqkv, w.wqkv_sb, w.bqkv, a->qkv, QKV, B, D, Hq, Hkv, hd, a->pos,
-                                          a->ctx, m->g.inv_freq, m->kv.block_table, m->kv.max_pages, kp, vp, m->tune.mfma_gemv,
+                                          slot, m->g.inv_freq, m->kv.block_table, m->kv.max_pages, kp, vp, m->tune.mfma_gemv,
                                           m->mfma_ws, qk_scale, c.rope_long_from, stream)); ++n;
     } else {
-      TRY(vlm_gemv_qkv_rope_kvwrite_ex(a->h, w.ln1_w, c.rms_eps, w.wqkv, w.bqkv, a->qkv, QKV, B, D, Hq, Hkv, hd, a->pos, a->ctx,
+      TRY(vlm_gemv_qkv_rope_kvwrite_ex(a->h, w.ln1_w, c.rms_eps, w.wqkv, w.bqkv, a->qkv, QKV, B, D, Hq, Hkv, hd, a->pos, slot,
                                        m->g.inv_freq, m->kv.block_table, m->kv.max_pages, kp, vp, m->tune.mfma_gemv, m->mfma_ws,
                                        qk_scale, c.rope_long_from, stream)); ++n;
     }
@@ -471,19 +495,19 @@ static int decode_impl(Llm* m, const vlm_decode_args* a, void* stream, int* laun
   }
   if (sample) {
     if (fused_tail) {
-      TRY(vlm_sample_greedy_advance(a->logits, VL, B, c.vocab, a->logprobs, VL, a->tok, a->sample_ws, a->ctx, a->pos,
-                                    a->out_ring, a->ring_len, a->step, m->g.embed, a->h, D, D, stream)); n += 2;
+      TRY(vlm_sample_greedy_advance_win(a->logits, VL, B, c.vocab, a->logprobs, VL, a->tok, a->sample_ws, a->ctx, a->pos,
+                                        a->out_ring, a->ring_len, a->step, m->g.embed, a->h, D, D, wn, stream)); n += 2;
     } else if (fused_sampled) {
       TRY(vlm_sample_advance(a->logits, VL, B, c.vocab, a->logprobs, a->scratch, VL, a->tok, a->sample_ws, a->temperature, a->top_p,
                              a->min_p, a->top_k, a->seed, a->ctx, a->pos, a->out_ring, a->ring_len, a->step, m->g.embed, a->h, D, D,
-                             stream));
+                             wn, stream));
       n += vlm_sample_last_launches();          // (the split top-p route issues more launches than the one-workgroup filter)
     } else {
       TRY(vlm_sample(a->logits, VL, B, c.vocab, a->logprobs, a->scratch, VL, a->tok, a->sample_ws, a->temperature, a->top_p,
                      a->min_p, a->top_k, a->seed, a->step, stream));
       // (greedy: partials, log-probs + candidates, pick; sampling: + the draw's partials, + the filter kernel(s) when one is on)
       n += vlm_sample_last_launches();
-      TRY(vlm_decode_advance(a->ctx, a->pos, a->tok, a->out_ring, a->ring_len, a->step, B, stream)); ++n;
+      TRY(vlm_decode_advance_win(a->ctx, a->pos, a->tok, a->out_ring, a->ring_len, a->step, B, wn, stream)); ++n;
     }
   }
   if (launches) *launches = n;
@@ -511,8 +535,9 @@ extern "C" int vlm_llm_decode_graph_build(void* handle, const vlm_decode_args* a
   (void)stream;
   Llm* m = static_cast<Llm*>(handle);
   if (!m || !a || a->B <= 0 || !m->kv.kpool) return 1;
+  const VlmWindow wn = window_of(m->tune, a->flags);
   for (DecodeGraph& g : m->graphs) {
-    if (same_key(g, *a, m->kv)) {
+    if (same_key(g, *a, m->kv, wn)) {
       g.last_use = ++m->tick;
       m->exec = g.exec;
       m->launches = g.launches;
@@ -523,7 +548,7 @@ extern "C" int vlm_llm_decode_graph_build(void* handle, const vlm_decode_args* a
   hipStream_t cap = nullptr;
   hipError_t e = hipStreamCreateWithFlags(&cap, hipStreamNonBlocking);
   if (e != hipSuccess) return 1000 + (int)e;
-  DecodeGraph ng{a->penalties ? *a->penalties : vlm_penalty_args{}, *a, m->kv, nullptr, nullptr, 0, ++m->tick};
+  DecodeGraph ng{a->penalties ? *a->penalties : vlm_penalty_args{}, *a, m->kv, wn, nullptr, nullptr, 0, ++m->tick};
   // wide steps run split-K GEMMs: the capture stream borrows the launch stream's workspace (the replays are ordered there)
   const bool wide = a->B > 16;
   if (wide && vlm_gemm_splitk_share(stream, (void*)cap) != 0) { (void)hipStreamDestroy(cap); return 1008; }

@@ -71,14 +71,41 @@ VLM_INTERNAL int vlm_gemv_mfma_rows_ok(int M, int N, int K);      // 1: vlm_gemv
 VLM_INTERNAL int vlm_gemv_mfma_rows_try(const void* xt, const void* W, const void* bias, const void* res, void* y, int M, int N, int K,
                                         int ldw, int ldy, int ldres, int epilogue, void* stream);
 
+// ---- max_kv_size on the device (VLM_DECODE_WINDOW, include/vlm_hip.h): the window rule of a decode step's tail.
+// M == 0: no window - ctx / pos are int32 [B] and both advance by one (the public entry points' behaviour).
+// M > 0: ctx = [2][B] (n = entries held, w = write slot), pos = [2][B] (p = rope position, d = rope delta); host mirror:
+// models/cache.py::window_step (tests/test_window_rule_cpu.py pins both to the reference's RotatingKVCache)
+struct VlmWindow {
+  int M, K, ring_pos;
+};
+__device__ __forceinline__ void vlm_window_advance(int* ctx, int* pos, int B, int b, const VlmWindow wn) {
+  if (wn.M <= 0) {
+    ctx[b] += 1;
+    pos[b] += 1;
+    return;
+  }
+  const int n = ctx[b], w = ctx[B + b], p = pos[b], d = pos[B + b];
+  ctx[b] = n + 1 < wn.M - 1 ? n + 1 : wn.M - 1;
+  ctx[B + b] = w + 1 == wn.M ? wn.K : w + 1;
+  const int r = p - d;                       // the ring's write index as the forward of this step read it
+  pos[b] = wn.ring_pos ? (r >= wn.M ? wn.K : r) + 1 + d : p + 1;
+}
+/* embed.hip: vlm_decode_advance under the window rule */
+VLM_INTERNAL int vlm_decode_advance_win(void* ctx, void* pos, const void* tok, void* out_ring, int ring_len, void* step, int B,
+                                        VlmWindow wn, void* stream);
+/* sample.hip: vlm_sample_greedy_advance under the window rule */
+VLM_INTERNAL int vlm_sample_greedy_advance_win(const void* logits, int ld, int B, int V, void* logprobs, int ldlp, void* tok,
+                                               void* workspace, void* ctx, void* pos, void* out_ring, int ring_len, void* step,
+                                               const void* embed, void* h, int D, int ldh, VlmWindow wn, void* stream);
+
 VLM_INTERNAL int vlm_sample_last_launches(void);   /* sample.hip: kernels the last vlm_sample / vlm_sample_advance of this thread enqueued */
 
 /* sample.hip: the sampled step's tail for the engine's captured step - vlm_sample (temperature > 0; top_p / min_p / top_k) with the
- * final pick, vlm_decode_advance and the next step's embedding gather in ONE last launch */
+ * final pick, vlm_decode_advance (under the window rule when wn.M > 0) and the next step's embedding gather in ONE last launch */
 VLM_INTERNAL int vlm_sample_advance(const void* logits, int ld, int B, int V, void* logprobs, void* scratch, int ldlp, void* tok,
                                     void* workspace, float temperature, float top_p, float min_p, int top_k, unsigned seed,
                                     void* ctx, void* pos, void* out_ring, int ring_len, void* step, const void* embed, void* h,
-                                    int D, int ldh, void* stream);
+                                    int D, int ldh, VlmWindow wn, void* stream);
 
 
 /* gemm_bf16.hip: what the reduce launch of a split-K GEMM does ON TOP of its epilogue (the wide decode steps of engine.hip): the

@@ -126,6 +126,7 @@ struct SampleTail {
   const bf16_t* embed;
   bf16_t* h;
   int D, ldh;
+  VlmWindow wn;          // M == 0: ctx / pos int32 [B], both + 1; M > 0: the window rule over int32 [2][B] (internal.h)
 };
 
 // the next step's input rows h[r] = embed[tok[r]] by ONE workgroup (the last block of a fused tail): 8 loads of a thread in flight
@@ -168,8 +169,7 @@ __global__ __launch_bounds__(256) void argmax_final_advance_kernel(const float* 
   if (tid < B) {
     const int y = s_tok[tid];
     tok[tid] = y;
-    t.ctx[tid] += 1;
-    t.pos[tid] += 1;
+    vlm_window_advance(t.ctx, t.pos, B, tid, t.wn);
     if (t.out_ring) t.out_ring[(size_t)(st % t.ring_len) * B + tid] = y;
   }
   gather_rows_256(t.embed, t.h, s_tok, B, t.D, t.ldh, tid);
@@ -192,7 +192,7 @@ __global__ __launch_bounds__(256) void logprob_argmax_tail_kernel(
     const bf16_t* __restrict__ logits, int ld, int V, const float* __restrict__ ws, bf16_t* __restrict__ logprobs, int ldlp,
     float* cand_v, int* cand_i, unsigned* ticket, int* __restrict__ tok, int* __restrict__ ctx, int* __restrict__ pos,
     int* __restrict__ out_ring, int ring_len, int* __restrict__ step, const bf16_t* __restrict__ embed,
-    bf16_t* __restrict__ h, int D, int ldh, int B) {
+    bf16_t* __restrict__ h, int D, int ldh, int B, VlmWindow wn) {
   __shared__ float sv[4];
   __shared__ int si[4];
   __shared__ int s_last;
@@ -291,8 +291,7 @@ __global__ __launch_bounds__(256) void logprob_argmax_tail_kernel(
   if (tid < B) {
     const int t = s_tok[tid];
     tok[tid] = t;
-    ctx[tid] += 1;
-    pos[tid] += 1;
+    vlm_window_advance(ctx, pos, B, tid, wn);
     if (out_ring) out_ring[(size_t)(st % ring_len) * B + tid] = t;
   }
   // next step's input embeddings
@@ -1645,8 +1644,9 @@ extern "C" int vlm_sample_ex(const void* logits, int ld, int B, int V, void* log
 VLM_INTERNAL int vlm_sample_advance(const void* logits, int ld, int B, int V, void* logprobs, void* scratch, int ldlp, void* tok,
                                     void* workspace, float temperature, float top_p, float min_p, int top_k, unsigned seed,
                                     void* ctx, void* pos, void* out_ring, int ring_len, void* step, const void* embed, void* h,
-                                    int D, int ldh, void* stream) {
+                                    int D, int ldh, VlmWindow wn, void* stream) {
   if (!(temperature > 0.f) || !ctx || !pos || !step || !embed || !h) return VLM_ERR_ARG;
+  if (wn.M > 0 && (wn.K < 0 || wn.M <= wn.K + 1)) return VLM_ERR_ARG;
   if (B > 64 || D % 8 || ldh % 8 || (out_ring && ring_len <= 0)) return VLM_ERR_SHAPE;
   vlm_sampler_params sp{};
   sp.temperature = temperature;
@@ -1656,7 +1656,7 @@ VLM_INTERNAL int vlm_sample_advance(const void* logits, int ld, int B, int V, vo
   sp.top_k = top_k;
   sp.typical_p = 1.0;
   sp.seed = seed;
-  const SampleTail t{(int*)ctx, (int*)pos, (int*)out_ring, (int*)step, ring_len, (const bf16_t*)embed, (bf16_t*)h, D, ldh};
+  const SampleTail t{(int*)ctx, (int*)pos, (int*)out_ring, (int*)step, ring_len, (const bf16_t*)embed, (bf16_t*)h, D, ldh, wn};
   return sample_ex_impl(logits, ld, B, V, logprobs, scratch, ldlp, tok, workspace, &sp, step, stream, &t);
 }
 
@@ -1680,7 +1680,16 @@ extern "C" int vlm_sample(const void* logits, int ld, int B, int V, void* logpro
 extern "C" int vlm_sample_greedy_advance(const void* logits, int ld, int B, int V, void* logprobs, int ldlp, void* tok,
                                          void* workspace, void* ctx, void* pos, void* out_ring, int ring_len, void* step,
                                          const void* embed, void* h, int D, int ldh, void* stream) {
+  return vlm_sample_greedy_advance_win(logits, ld, B, V, logprobs, ldlp, tok, workspace, ctx, pos, out_ring, ring_len, step, embed, h,
+                                       D, ldh, VlmWindow{0, 0, 0}, stream);
+}
+
+/* ... with the window rule in the last block's bookkeeping (wn.M > 0: ctx / pos are int32 [2][B], internal.h) */
+VLM_INTERNAL int vlm_sample_greedy_advance_win(const void* logits, int ld, int B, int V, void* logprobs, int ldlp, void* tok,
+                                               void* workspace, void* ctx, void* pos, void* out_ring, int ring_len, void* step,
+                                               const void* embed, void* h, int D, int ldh, VlmWindow wn, void* stream) {
   if (!logits || !tok || !workspace || !ctx || !pos || !step || !embed || !h || B <= 0 || V <= 0) return VLM_ERR_ARG;
+  if (wn.M > 0 && (wn.K < 0 || wn.M <= wn.K + 1)) return VLM_ERR_ARG;
   if (B > TAIL_MAX_B || D % 8 || ldh % 8) return VLM_ERR_SHAPE;
   if (out_ring && ring_len <= 0) return VLM_ERR_ARG;
   hipStream_t st = (hipStream_t)stream;
@@ -1692,7 +1701,7 @@ extern "C" int vlm_sample_greedy_advance(const void* logits, int ld, int B, int 
   VLM_CHECK_LAUNCH();
   hipLaunchKernelGGL(logprob_argmax_tail_kernel, dim3(NBLK, B), dim3(256), 0, st, (const bf16_t*)logits, ld, V, ws,
                      (bf16_t*)logprobs, ldlp, cand_v, cand_i, ticket, (int*)tok, (int*)ctx, (int*)pos, (int*)out_ring, ring_len,
-                     (int*)step, (const bf16_t*)embed, (bf16_t*)h, D, ldh, B);
+                     (int*)step, (const bf16_t*)embed, (bf16_t*)h, D, ldh, B, wn);
   VLM_CHECK_LAUNCH();
   return VLM_OK;
 }

@@ -279,7 +279,8 @@ def generate_step(input_ids, model, pixel_values, mask, *, max_tokens: int = DEF
         # without telling the caller
         raise NotImplementedError("draft_model is outside the built hot path (SURVEY section 8f.4)")
     # reference ar.py:173,310-315: make_prompt_cache(model.language_model, max_kv_size) - a RotatingKVCache(max_kv_size, keep=4)
-    # per layer when the caller brings no prompt_cache.  Here: a bound on the paged sequence, served by eager steps
+    # per layer when the caller brings no prompt_cache.  Here: a bound on the paged sequence; its decode steps run captured over
+    # the device-resident window (LanguageModel.decode_begin), eagerly only for what cannot live in a captured step
     max_kv_size = kwargs.pop("max_kv_size", None)
     # uniform quantized KV cache (reference ar.py:174-181,249-260,362: maybe_quantize_kv_cache after EVERY forward): from the
     # first forward that leaves the cache at quantized_kv_start tokens or more, the cache is a QuantizedKVCache
@@ -301,7 +302,7 @@ def generate_step(input_ids, model, pixel_values, mask, *, max_tokens: int = DEF
         # an extended Sampler runs through its __call__, whose RNG step is a counter of the object: like the captured path
         # (step 0 at the start of every generation) a seeded sampler reused across two generations draws the same stream
         py_sampler._calls = 0
-    eager = bool(py_procs) or py_sampler is not None or thinking_budget_criteria is not None or max_kv_size is not None
+    eager = bool(py_procs) or py_sampler is not None or thinking_budget_criteria is not None
     lm = model.language_model
 
     ids = input_ids.detach().cpu().numpy() if isinstance(input_ids, torch.Tensor) else np.asarray(input_ids)
@@ -321,8 +322,12 @@ def generate_step(input_ids, model, pixel_values, mask, *, max_tokens: int = DEF
     own_cache = prompt_cache is None
     if own_cache:
         prompt_cache = cache_mod.make_prompt_cache(lm, max_kv_size=max_kv_size)
-    if prompt_cache[0]._seq.rotating:
-        eager = True                                   # (also a caller's own make_prompt_cache(lm, max_kv_size=...))
+    if prompt_cache[0]._seq.rotating:                  # (also a caller's own make_prompt_cache(lm, max_kv_size=...))
+        # two rope tables (Phi-3.5-vision: the qkv epilogue reads the slot as the cache offset) and a window that already
+        # wrapped on the host-planned arrangement stay on the eager path
+        supports = getattr(lm, "supports_window_decode", None)
+        if supports is None or not supports() or prompt_cache[0]._seq.ring is not None:
+            eager = True
         if kv_bits is not None:
             raise NotImplementedError("RotatingKVCache Quantization NYI")          # the reference's words (cache.py:583-584)
         # the reference prefills prompts beyond prefill_step_size in chunks (ar.py:425-470) and a rotating cache trims its
@@ -391,6 +396,12 @@ def generate_step(input_ids, model, pixel_values, mask, *, max_tokens: int = DEF
     base_offset = seq.offset
 
     lookahead = max(1, min(int(lookahead), st.ring_len - 1))
+    win0 = seq.window_state() if st.window is not None else None
+    if st.window is not None and not own_cache:
+        # steps enqueued ahead of the consumer overwrite the oldest entries of a window (an unbounded cache only writes slots the
+        # offset does not count yet).  A cache the caller keeps: one step ahead, the reference's own state at a yield (its `_step`
+        # runs one token ahead, ar.py:498-508) - the step the bookkeeping below takes back rewrites the very slot it wrote
+        lookahead = 1
     pipe = _TokenPipe(1, cap=lookahead + 2)
     pipe.push(0, tok0)
     lps: List[Optional[torch.Tensor]] = [lp0[0] if lp0 is not None else None] + [None] * (lookahead + 1)
@@ -412,7 +423,11 @@ def generate_step(input_ids, model, pixel_values, mask, *, max_tokens: int = DEF
     finally:
         # the cache holds prompt + the tokens that were FED back: every yielded token except the last (steps enqueued
         # ahead of the caller wrote further slots; they are overwritten when decoding continues from this offset)
-        seq.offset = base_offset + max(0, min(n, issued + 1) - 1)
+        fed = max(0, min(n, issued + 1) - 1)
+        seq.offset = base_offset + fed
+        if win0 is not None:               # the host's window state: that of "tokens fed"
+            seq.window_restore(win0)
+            seq.window_advance(fed)
         if own_cache:
             seq.release()
 

@@ -27,6 +27,31 @@ PAGE = 64
 VSLOT = [(w & 32) + 8 * (((w & 31) & 15) >> 2) + 4 * ((w & 31) >> 4) + (w & 3) for w in range(PAGE)]
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# max_kv_size as a DEVICE-RESIDENT window (reference RotatingKVCache, cache.py:442-625): the host mirror of the rule the
+# engine's decode tails apply (csrc/internal.h vlm_window_advance; include/vlm_hip.h VLM_DECODE_WINDOW).  Per row:
+#   n = entries held before the step's write, w = the slot the step writes, r = the ring's write index as the step's forward
+#   reads it (the reference's `_idx`; a family that reads it as its offset has rope position p = r + delta).
+# The pool holds token t of the window at slot t (t < keep: the sinks) or at slot keep + (t - keep) mod (M - keep) - the
+# reference's ring order; attention does not care about slot order (the rotation is baked into the keys).
+def window_start(L: int, M: int, K: int):
+    """State after a FIRST prompt of L tokens (written at slots 0..L-1) -> (n, w, src_slots, dst_slots): the entries that have to
+    move (one vlm_kv_move_tokens call; sources in [M, L), destinations in [K, M), disjoint) so that every survivor sits at its
+    ring slot.  The entry the reference overwrites first is never copied: it sits at w."""
+    L, M, K = int(L), int(M), int(K)
+    if L < M:
+        return L, L, [], []
+    R = M - K
+    src = [t for t in range(L - R + 1, L) if t >= M]
+    dst = [K + (t - K) % R for t in src]
+    return M - 1, K + (L - K) % R, src, dst
+
+
+def window_step(n: int, w: int, r: int, M: int, K: int):
+    """one decode step: -> (n', w', r')"""
+    return min(n + 1, M - 1), (K if w + 1 == M else w + 1), (K if r >= M else r) + 1
+
+
 class Arena:
     """One contiguous device allocation carved into the engine's SMALL buffers (decode state, block table, norm
     weights, biases, ...).  Measured on MI355X: the first access of a kernel to each separately allocated small
@@ -190,6 +215,10 @@ class PagedSequence:
         self.held = 0
         self.ring = None
         self.ring_idx = 0        # the reference's `_idx` (what its Qwen2-VL reads as the cache offset, language.py:426-431)
+        # the DEVICE-RESIDENT arrangement (window_start / window_step above): the slot the next decode step writes; None = the
+        # sequence is not on it (no window, or the host-planned arrangement of rotate_plan).  With it `held` is the rule's n and
+        # `ring_idx` its r; `ring` stays None
+        self.win_w: Optional[int] = None
 
     # ------------------------------------------------------------------ per-layer appends (update_and_fetch)
     def layer_offset(self, layer: int) -> int:
@@ -248,6 +277,8 @@ class PagedSequence:
         ring_idx as the reference's trim + wrap do."""
         if not self.rotating:
             return None
+        if self.win_w is not None:
+            raise RuntimeError("rotate_plan on a sequence whose window lives on the device (window_enter)")
         M, K = self.max_size, self.keep
         plan = None
         if self.held > M:
@@ -276,6 +307,30 @@ class PagedSequence:
                 self.ring_idx = K
             plan = ([M - 1], [oldest])
         return plan
+
+    # ---- the device-resident arrangement
+    def window_enter(self):
+        """Move to the device-resident arrangement: possible while the host-planned one has not wrapped (`ring is None`: every
+        entry still sits at slot = token index).  -> (src_slots, dst_slots) for ONE vlm_kv_move_tokens call (empty lists: nothing
+        moves); the caller enqueues it before the first window step."""
+        if not self.rotating or self.ring is not None:
+            raise NotImplementedError("max_kv_size: this window already wrapped on the host-planned arrangement (module calls); "
+                                      "it stays on the one-step-at-a-time path")
+        if self.win_w is not None:
+            return [], []
+        self.held, self.win_w, src, dst = window_start(self.held, self.max_size, self.keep)
+        return src, dst
+
+    def window_advance(self, steps: int = 1):
+        """`steps` window steps were enqueued (the device advanced itself: no read-back)"""
+        for _ in range(int(steps)):
+            self.held, self.win_w, self.ring_idx = window_step(self.held, self.win_w, self.ring_idx, self.max_size, self.keep)
+
+    def window_state(self):
+        return self.held, self.win_w, self.ring_idx
+
+    def window_restore(self, state):
+        self.held, self.win_w, self.ring_idx = state
 
     def note_decode_step(self):
         """one token was written at slot `held` (ring position ring_idx) and the offset grew"""
@@ -401,13 +456,15 @@ class KVCache:
         s = self._seq
         n = min(s.offset, n)
         if self._layer == 0:
-            if s.rotating and n and s.ring is not None:
+            if s.rotating and n and (s.ring is not None or (s.win_w is not None and s.offset >= s.max_size)):
                 raise NotImplementedError("trim of a rotating cache whose window has wrapped (the reference moves offset and _idx "
                                           "only, cache.py:577-581: its buffer then holds tokens the offset no longer counts)")
             s.set_offset(s.offset - n)
             if s.rotating:
                 s.held -= n
                 s.ring_idx -= n
+                if s.win_w is not None:          # (not wrapped yet: slot == token index)
+                    s.win_w -= n
         return n
 
     @property

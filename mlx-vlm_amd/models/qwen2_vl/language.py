@@ -50,8 +50,12 @@ class DecodeState:
         self.B, self.nsplit, self.ring_len = B, nsplit, ring_len   # nsplit: buffers sized for the max, see decode_begin
         A = lm.arena.alloc
         self.tok = A(B, i32, zero=True)
-        self.pos = A(B, i32, zero=True)
-        self.ctx = A(B, i32, zero=True)
+        # [2][B] each: row 0 is what every step reads (rope position / entries held); row 1 belongs to the window mode of a step
+        # (_lib.DECODE_WINDOW: pos row 1 = rope delta, ctx row 1 = the slot the step writes) and is unused where nothing rotates
+        self.pos2 = A((2, B), i32, zero=True)
+        self.ctx2 = A((2, B), i32, zero=True)
+        self.pos, self.ctx = self.pos2[0], self.ctx2[0]
+        self.window = None          # (M, K, ring_pos) while the bound sequences decode on the device-resident window
         self.step = A(1, i32, zero=True)
         self.h = A((B, D), bf)
         self.qkv = A((B, (Hq + 2 * Hkv) * hd), bf)
@@ -708,6 +712,49 @@ class LanguageModel:
             self._keep_rot = dev
         return rope_pos
 
+    def supports_window_decode(self) -> bool:
+        """can a decode step of this model run in window mode (_lib.DECODE_WINDOW)?  Not with two rope tables: that qkv epilogue
+        derives the long-factor regime from the rows' cache offsets, which the window's slot no longer is (Phi-3.5-vision)"""
+        return not int(getattr(self, "rope_long_from", 0) or 0)
+
+    def _window_begin(self, seqs):
+        """Rows with max_kv_size enter (or continue on) the device-resident window: at most ONE vlm_kv_move_tokens call for the
+        rows whose first prompt was longer than the window (models/cache.py::window_start).  -> (M, K, ring_pos)"""
+        if not all(s.rotating for s in seqs) or len({(s.max_size, s.keep) for s in seqs}) != 1:
+            raise NotImplementedError("max_kv_size: the rows of one decode step share one window (max_kv_size, keep)")
+        if any(s.q8 for s in seqs):
+            raise NotImplementedError("RotatingKVCache Quantization NYI")          # (the reference's own words, cache.py:583-584)
+        if not self.supports_window_decode() or len(seqs) not in (1, 2, 4, 8):
+            raise NotImplementedError("max_kv_size: the captured window step is built for 1 / 2 / 4 / 8 rows of a one-table rope "
+                                      "model; this one runs through the module call, one step at a time")
+        if any(s.ring is not None for s in seqs):
+            raise NotImplementedError("max_kv_size: the captured step writes at the ring slot of the device-resident window; a "
+                                      "window that already wrapped through module calls (LanguageModel.__call__) stays on them")
+        rows, src, dst = [], [], []
+        for s in seqs:
+            a, d = s.window_enter()
+            rows += [s.seq] * len(a)
+            src += a
+            dst += d
+        if rows:
+            pool = self.pool
+            dev = _lib.h2d(np.array([rows, src, dst], dtype=np.int32), self.device)
+            check(_lib.lib().vlm_kv_move_tokens(pool.kpool.data_ptr(), pool.vpool.data_ptr(), pool.layer_stride, pool.n_layers,
+                                                dev[0].data_ptr(), dev[1].data_ptr(), dev[2].data_ptr(), len(rows),
+                                                pool.block_table.data_ptr(), pool.max_pages, pool.n_kv_heads, pool.head_dim,
+                                                C.c_void_p(torch.cuda.current_stream().cuda_stream)), "kv_move_tokens")
+            self._keep_rot = dev
+        return (seqs[0].max_size, seqs[0].keep, int(bool(self.ROTATING_POS_FROM_RING)))
+
+    def _set_window_mode(self, window):
+        """the handle's mode values of a window step (vlm_llm_set_tuning keys 16..18); a change drops the engine's graphs"""
+        if getattr(self, "_window_mode", (0, 0, 0)) != tuple(window):
+            for k, v in zip((_lib.MODE_WINDOW_SIZE, _lib.MODE_WINDOW_KEEP, _lib.MODE_WINDOW_RING_POS), window):
+                check(_lib.lib().vlm_llm_set_tuning(self._handle, k, int(v)), "llm_set_tuning")
+            self._window_mode = tuple(window)
+            for st in self._decode_states.values():
+                st.graph_key = None
+
     def decode_begin(self, caches: List[List[KVCache]], first_tokens, rope_deltas, max_new_tokens: int, rope_pos=None) -> DecodeState:
         """Bind B sequences (B in {1,2,4,8}) to the device decode state: tok = first sampled tokens,
         ctx = cache offsets, pos = offset + rope_delta (reference language.py:476-509)."""
@@ -716,10 +763,15 @@ class LanguageModel:
         seqs = [c[0]._seq for c in caches]
         for s in seqs:
             s.reserve(s.offset + max_new_tokens + 1)
+        # max_kv_size without `rope_pos` (the caller did not make room on the host): the rows go to - or continue on - the
+        # device-resident window, where a decode step advances the ring itself
+        st.window = self._window_begin(seqs) if rope_pos is None and any(s.rotating for s in seqs) else None
         # attention decomposition for this generation: up to 2048 tokens one workgroup per (sequence, kv head)
         # walks the pages itself (nsplit = 1, no merge pass); beyond that, split-K with one workgroup per
         # page-stride (<= 32 splits) merged in the o_proj prologue
         max_total = max(s.kv_entries for s in seqs) + max_new_tokens + 1
+        if st.window is not None:            # (a window never holds more than max_kv_size entries)
+            max_total = min(max_total, st.window[0])
         st.nsplit = 1 if max_total <= 2048 else max(2, min(32, (max_total + 16 * PAGE - 1) // (16 * PAGE)))
         if os.environ.get("VLM_DECODE_NSPLIT"):     # A/B knob for measurements
             st.nsplit = max(1, min(32, int(os.environ["VLM_DECODE_NSPLIT"])))
@@ -731,11 +783,18 @@ class LanguageModel:
         # (a rotating window: entries held, not tokens seen; the rope offset is the family's - `rope_pos` when the caller read it
         # before the window wrapped, LanguageModel.__call__)
         ctx = np.array([s.kv_entries for s in seqs], dtype=np.int32)
-        base = np.array([s.offset for s in seqs], dtype=np.int32) if rope_pos is None else np.asarray(rope_pos, dtype=np.int32)
-        pos = base + np.asarray(rope_deltas, dtype=np.int64).reshape(-1).astype(np.int32)
-        host = np.concatenate([pos, ctx, np.zeros(1, np.int32)])
+        if rope_pos is not None:
+            base = np.asarray(rope_pos, dtype=np.int32)
+        elif st.window is not None and st.window[2]:
+            base = np.array([s.ring_idx for s in seqs], dtype=np.int32)
+        else:
+            base = np.array([s.offset for s in seqs], dtype=np.int32)
+        delta = np.asarray(rope_deltas, dtype=np.int64).reshape(-1).astype(np.int32)
+        pos = base + delta
+        slot = np.array([s.win_w for s in seqs], dtype=np.int32) if st.window is not None else ctx
+        host = np.concatenate([pos, delta, ctx, slot, np.zeros(1, np.int32)])
         dev = _lib.h2d(host, self.device)
-        st.pos.copy_(dev[:B]); st.ctx.copy_(dev[B:2 * B]); st.step.copy_(dev[2 * B:])
+        st.pos2.view(-1).copy_(dev[:2 * B]); st.ctx2.view(-1).copy_(dev[2 * B:4 * B]); st.step.copy_(dev[4 * B:])
         if isinstance(first_tokens, torch.Tensor):
             st.tok.copy_(first_tokens.reshape(-1).to(torch.int32))
         else:
@@ -791,9 +850,13 @@ class LanguageModel:
     def decode_run(self, st: DecodeState, n_steps: int, sampler_args: dict, use_graph: bool = True, penalties=None):
         """Enqueue n_steps decode steps (graph replays when use_graph).  penalties: sample_utils.LogitsProcessors."""
         L = _lib.lib()
-        if any(s.rotating for s in st.seqs):
+        if st.window is None and any(s.rotating for s in st.seqs):
             raise NotImplementedError("max_kv_size: the captured step writes at slot = tokens seen; a rotating window runs "
                                       "through the module call (LanguageModel.__call__), one step at a time")
+        if st.window is not None:
+            if any(s.win_w is None for s in st.seqs):
+                raise RuntimeError("decode_run: the state's rows left the device-resident window (decode_begin binds them)")
+            self._set_window_mode(st.window)
         stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
         q8 = self._seqs_q8(st.seqs)
         kv = self._kv_struct(st.seq_row0, decode=True, q8=q8)
@@ -801,11 +864,13 @@ class LanguageModel:
         # the fused tails (greedy: vlm_sample_greedy_advance; with a temperature: the sampler's last launch also advances and
         # gathers) read bf16 embedding rows
         fused = bool(self.tuning.get("fused_tail")) and not hasattr(self._w["embed"], "wq")
-        args = st.args(flags=_lib.DECODE_FUSED_TAIL if fused else 0, penalties=penalties, **sampler_args)
+        flags = (_lib.DECODE_FUSED_TAIL if fused else 0) | (_lib.DECODE_WINDOW if st.window is not None else 0)
+        args = st.args(flags=flags, penalties=penalties, **sampler_args)
         if os.environ.get("VLM_NO_GRAPH"):           # diagnostics: every launch of the step visible to the HIP runtime's log
             use_graph = False
         if use_graph:
-            key = (st.seq_row0, st.nsplit, fused, q8, penalties.key() if penalties else None, tuple(sorted(sampler_args.items())))
+            key = (st.seq_row0, st.nsplit, fused, q8, st.window, penalties.key() if penalties else None,
+                   tuple(sorted(sampler_args.items())))
             if st.graph_key != key or getattr(self, "_graph_owner", None) is not st:
                 check(L.vlm_llm_decode_graph_build(self._handle, C.byref(args), stream), "decode_graph_build")
                 st.graph_key = key
@@ -817,6 +882,8 @@ class LanguageModel:
                 check(L.vlm_llm_decode_step(self._handle, C.byref(args), stream), "decode_step")
         for s in st.seqs:
             s.offset += n_steps
+            if st.window is not None:       # the device advanced (n, w, p) itself; the host's mirror follows from the rule alone
+                s.window_advance(n_steps)
 
     @staticmethod
     def _seqs_q8(seqs) -> bool:
@@ -904,25 +971,33 @@ class LanguageModel:
             deltas = np.broadcast_to(np.asarray(deltas).reshape(-1, 1), (B, 1)) if np.asarray(deltas).size == 1 else deltas
             rope_pos = None
             rot = [c[0]._seq for c in caches if c[0]._seq.rotating]
-            saved = [(s, s.held, None if s.ring is None else list(s.ring), s.ring_idx) for s in rot]
+            # rows already on the device-resident window (a captured run came first) continue there: ONE window step through
+            # vlm_llm_decode_forward from the host's mirror - one arrangement per sequence.  The others keep the host-planned ring
+            on_device = any(s.win_w is not None for s in rot)
+            saved = [(s, s.held, None if s.ring is None else list(s.ring), s.ring_idx, s.win_w) for s in rot]
             try:
-                if rot:
+                if rot and not on_device:
                     rope_pos = self._rotate_windows([c[0]._seq for c in caches])
                 st = self.decode_begin(caches, ids.reshape(-1), deltas[:B], max_new_tokens=1, rope_pos=rope_pos)
                 kv = self._kv_struct(st.seq_row0, decode=B <= 16, q8=self._seqs_q8(st.seqs))
                 check(_lib.lib().vlm_llm_set_kv(self._handle, C.byref(kv)), "llm_set_kv")
-                args = st.args()
+                if st.window is not None:
+                    self._set_window_mode(st.window)
+                args = st.args(flags=_lib.DECODE_WINDOW if st.window is not None else 0)
                 check(_lib.lib().vlm_llm_decode_forward(self._handle, C.byref(args),
                                                         C.c_void_p(torch.cuda.current_stream().cuda_stream)), "decode_forward")
             except Exception:
                 # the step did not get enqueued (slot rows, pool exhaustion, ...): the ring goes back to what it was, so a retry
                 # plans the SAME move again (newest entry -> the slot of the token that leaves: idempotent on the pool)
-                for s, held, ring, ring_idx in saved:
-                    s.held, s.ring, s.ring_idx = held, ring, ring_idx
+                for s, held, ring, ring_idx, win_w in saved:
+                    s.held, s.ring, s.ring_idx, s.win_w = held, ring, ring_idx, win_w
                 raise
             for s in st.seqs:
                 s.offset += 1
-                s.note_decode_step()
+                if st.window is not None:
+                    s.window_advance(1)
+                else:
+                    s.note_decode_step()
             return LanguageModelOutput(logits=st.logits.clone().view(B, 1, -1))
 
         # prefill path
