@@ -317,7 +317,15 @@ int vlm_sample(const void* logits, int ld, int B, int V, void* logprobs, void* s
  * per row], the Gumbel-max partials (64 workgroups per row), the final pick.
  * typical_p needs sort_workspace (device, vlm_sample_sort_workspace_bytes(B, V)).  xtc: B == 1 only (the reference's minimum
  * runs over the whole array and its draw is one scalar per call) -> VLM_ERR_SHAPE otherwise; the draw is the counter hash at
- * (seed, *step_ptr, row, 0xFFFFFFFF); xtc_special_tokens = device int32 [n_xtc_special <= 256]. */
+ * (seed, *step_ptr, row, 0xFFFFFFFF); xtc_special_tokens = device int32 [n_xtc_special <= 256].
+ *
+ * input_is_logprobs == 2 (added within ABI v8): top_logprobs mode - nothing is sampled.  `logits` = bf16 log-prob rows [B][ld]
+ * (ld >= V; what lies past V is never read, the rows are left untouched), top_k = K with 1 <= K <= min(64, V) (VLM_ERR_SHAPE
+ * otherwise), `tok` = int32 [B][K] out, `logprobs` = bf16 [B][K] out: the K best entries of every row as the reference's batch
+ * generator lists them (ar.py:1092-1122, argsort ascending, last K, reversed): value descending and, among equal values, the
+ * HIGHER index first; +0.0 and -0.0 are equal values; the value written is the row's own bits at that index.  NaN is outside the
+ * contract.  Every other field, `scratch`, `ldlp`, `workspace` and `step_ptr` are ignored (workspace may be NULL and is not
+ * touched).  One launch, one workgroup per row. */
 typedef struct vlm_sampler_params {
   double temperature, top_p, min_p;
   int min_tokens_to_keep, top_k;
@@ -329,7 +337,7 @@ typedef struct vlm_sampler_params {
   void* sort_workspace;
   unsigned seed;
   int input_is_logprobs; /* temperature > 0: `logits` already holds log-probs (what the reference hands a sampler closure,
-                            ar.py:368-379): no logsumexp pass, `logprobs` may be NULL */
+                            ar.py:368-379): no logsumexp pass, `logprobs` may be NULL.  2: top_logprobs mode, see above */
 } vlm_sampler_params;
 size_t vlm_sample_sort_workspace_bytes(int B, int V);
 int vlm_sample_ex(const void* logits, int ld, int B, int V, void* logprobs, void* scratch, int ldlp, void* tok, void* workspace,

@@ -71,6 +71,10 @@ class SamplerParams(C.Structure):
                 ("n_xtc_special", c_int), ("sort_workspace", c_void_p), ("seed", c_uint), ("input_is_logprobs", c_int)]
 
 
+SAMPLE_MODE_TOP_LOGPROBS = 2      # vlm_sampler_params.input_is_logprobs: the call lists the top_k best log-probs per row (ABI v8)
+TOP_LOGPROBS_MAX_K = 64           # the kernel's cap on K (csrc/top_logprobs.hip)
+
+
 class VitConfig(C.Structure):
     _fields_ = [("depth", c_int), ("embed_dim", c_int), ("n_heads", c_int), ("mlp_hidden", c_int), ("patch_k", c_int),
                 ("merge", c_int), ("out_dim", c_int), ("ln_eps", c_float), ("qk_interleaved", c_int)]

@@ -46,6 +46,7 @@ MAX_ROWS = 16         # default widest decode step: one N tile of the skinny-M M
 WIDE_ROWS = 64        # on request (completion_batch_size > 16): WIDE steps of 32 / 64 rows on the prefill GEMMs (engine.hip decode_impl:
                       # 192.6 us per Qwen2-VL-7B layer at 32 rows, 210 at 64, against 120 per 16-row step - profiles/r03_mfma_shapes.txt)
 WIDTHS = (1, 2, 4, 8, 16, 32, 64)
+MAX_TOP_LOGPROBS = 64  # top_logprobs_k: the selection kernel's cap (csrc/top_logprobs.hip)
 
 
 class _NullEvent:
@@ -100,6 +101,7 @@ class _Admission:
     joined: int = 0                # requests of `batch` already given a row (a join takes as many as there are free rows)
     done_t: Optional[float] = None # host clock when the prefill's event was first seen fired (it may WAIT for a row after that)
     pen: Any = None                # device (hist, hist_len, params, bias_idx, bias_val) of the admitted requests, or None
+    top0: Any = None               # top_logprobs_k > 0: (indices [n, k], values [n, k]) of the first tokens
 
     def waiting(self) -> int:
         return sum(1 for b in self.batch[self.joined:] if b[0] not in self.removed)
@@ -131,7 +133,9 @@ class BatchGenerator:
     (ar.py:1044-1141).  `thinking_budget_criteria` per request (ar.py:1303-1350).  `kv_bits=8`: the uniform 8-bit KV
     cache with the reference's batch policy (every layer but the last of a stack deeper than 2, models/cache.py:8-21);
     as in the reference's batch path `quantized_kv_start` has no effect on the uniform scheme (ar.py:776-812: the batch
-    caches are quantised from the first token).  APC and speculative drafts are outside the built path and are rejected."""
+    caches are quantised from the first token).  `top_logprobs_k=k` (ar.py:2209; k <= 64): every Response carries the k best
+    (token, log-prob) pairs of its token's log-prob row - after the logits processors, before the sampler's filters - in the
+    reference's order (ops.top_logprobs), selected by one HIP launch behind every step.  APC and speculative drafts are outside the built path and are rejected."""
 
     @dataclass
     class Response:
@@ -160,6 +164,16 @@ class BatchGenerator:
             # token; accepted and, as there, without effect
             if getattr(self.lm if hasattr(self, "lm") else model.language_model, "head_dim", 128) != 128:
                 raise NotImplementedError("BatchGenerator(kv_bits=8): the 8-bit KV kernels are built for 128-wide heads")
+        # top_logprobs_k (reference ar.py:2209): every Response carries the k best (token, log-prob) pairs of its token's row
+        k = kwargs.pop("top_logprobs_k", None)
+        k = 0 if k is None else k
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)):
+            raise TypeError(f"BatchGenerator: top_logprobs_k = {k!r}: an int >= 0")
+        if k < 0:
+            raise ValueError(f"BatchGenerator: top_logprobs_k = {k}: an int >= 0")
+        if k > MAX_TOP_LOGPROBS:
+            raise NotImplementedError(f"BatchGenerator: top_logprobs_k = {k}: at most {MAX_TOP_LOGPROBS} entries per token are built")
+        self.top_logprobs_k = int(k)
         if kwargs.get("max_kv_size"):
             # reference ar.py:831-834 (to_batch_cache): make_prompt_cache's RotatingKVCache has keep = 4
             raise ValueError("RotatingKVCache with keep tokens is not supported.")
@@ -223,6 +237,13 @@ class BatchGenerator:
         self._pin_lp = torch.empty(2, cap, dtype=torch.float32)
         if self._cuda:
             self._pin_tok, self._pin_lp = self._pin_tok.pin_memory(), self._pin_lp.pin_memory()
+        if self.top_logprobs_k:
+            # the k best (index, log-prob) of the token sitting in st.tok, beside self._lp, and their two pinned slots
+            self._top_idx, self._top_val = self._new_top_buffers(cap, self.top_logprobs_k)
+            self._pin_top_idx = torch.empty(2, cap, self.top_logprobs_k, dtype=self._top_idx.dtype)
+            self._pin_top_val = torch.empty(2, cap, self.top_logprobs_k, dtype=self._top_val.dtype)
+            if self._cuda:
+                self._pin_top_idx, self._pin_top_val = self._pin_top_idx.pin_memory(), self._pin_top_val.pin_memory()
         self._inflight: Optional[Tuple[int, torch.cuda.Event, List[int], float]] = None
         self._pending: List[_Admission] = []         # oldest first
         self._side = _admission_stream(dev) if (async_prefill and self._cuda) else None
@@ -242,6 +263,7 @@ class BatchGenerator:
         self._blocked = 0.0
 
     # ------------------------------------------------------------------ engine hooks
+    # (top_logprobs_k > 0 adds three, called only then: _new_top_buffers, _prefill_top_logprobs, _step_top_logprobs.)
     # Everything that touches the device sits behind these five methods; the scheduler (queue, admission, joins,
     # compaction, finish rules, stats) never looks past them, so it is driven by a mock engine in the CPU tests.
     def _event(self):
@@ -300,7 +322,10 @@ class BatchGenerator:
             _, lp = ops.sample(logits, want_logprobs=True, temperature=0.0)
             tok0 = self._call_sampler(lp)
         else:
-            tok0, lp = ops.sample(logits, step=step0, want_logprobs=self.compute_logprobs, **self._sargs)
+            tok0, lp = ops.sample(logits, step=step0, want_logprobs=self._want_rows(), **self._sargs)
+        # top_logprobs_k > 0: the first tokens' log-prob rows stay here for `_prefill_top_logprobs`, which `_admit_begin` calls
+        # right after this hook on the same stream (the 5-tuple below keeps its shape: the mock engines return it)
+        self._last_lp_rows = lp if self.top_logprobs_k else None
         lp0 = lp.gather(1, tok0.long()[:, None]).reshape(-1).float() if self.compute_logprobs else None
         ctx = np.asarray(lens, dtype=np.int32)
         state = h2d(np.stack([ctx + np.asarray(deltas, dtype=np.int32), ctx]), lm.device)
@@ -311,7 +336,7 @@ class BatchGenerator:
         if self._py_sampler is not None or any(row.py_procs for row in self._rows):
             return self._decode_rows_eager(width)
         self.lm.decode_step_rows(self._st, width, self._table, self._sargs, use_graph=self.use_graph,
-                                 with_logprobs=self.compute_logprobs, row_penalties=any(row.procs for row in self._rows),
+                                 with_logprobs=self._want_rows(), row_penalties=any(row.procs for row in self._rows),
                                  q8=self.kv_bits is not None)
 
     @staticmethod
@@ -346,7 +371,7 @@ class BatchGenerator:
             tok = torch.zeros(width, dtype=torch.int32, device=logits.device)
             tok[:n].copy_(self._call_sampler(lp[:n]))
         else:
-            tok, lp = ops.sample(logits, step=st.step, want_logprobs=self.compute_logprobs, **self._sargs)
+            tok, lp = ops.sample(logits, step=st.step, want_logprobs=self._want_rows(), **self._sargs)
         st.tok[:width].copy_(tok)
         if lp is not None:
             st.logprobs[:width].copy_(lp)
@@ -364,6 +389,33 @@ class BatchGenerator:
         """log-prob of the token each of the first n rows has just sampled (f32 [n])"""
         st = self._st
         return st.logprobs[:n].gather(1, st.tok[:n].long()[:, None]).reshape(-1).float()
+
+    def _want_rows(self) -> bool:
+        """the steps write the log-prob rows: for token_logprob, or for the top_logprobs selection"""
+        return bool(self.compute_logprobs or self.top_logprobs_k)
+
+    # ---- top_logprobs_k > 0 only (reference ar.py:1092-1122, 2051-2058: logprobs after the logits processors, before the
+    # sampler's filters, no temperature; argsort ascending, the last k, reversed - ops.top_logprobs states the order)
+    def _new_top_buffers(self, cap: int, k: int):
+        """-> (int32 [cap, k], bf16 [cap, k]) on the engine's device: the list of the token sitting in st.tok of every row"""
+        dev = self.lm.device
+        return (torch.zeros(cap, k, dtype=torch.int32, device=dev), torch.zeros(cap, k, dtype=torch.bfloat16, device=dev))
+
+    def _prefill_top_logprobs(self, batch):
+        """-> (indices [n, k], values [n, k]) of the first tokens `_prefill_requests(batch)` has just sampled: the selection
+        over the prefill's last-row log-probs, on the stream of the prefill.  Contract: called once, right after
+        `_prefill_requests(batch)`, which leaves those rows (after the requests' processors) in `self._last_lp_rows`; an engine
+        that replaces `_prefill_requests` replaces this hook too."""
+        lp, self._last_lp_rows = getattr(self, "_last_lp_rows", None), None
+        if lp is None or lp.shape[0] != len(batch):
+            raise RuntimeError("BatchGenerator._prefill_top_logprobs: no log-prob rows of this batch - _prefill_requests leaves them "
+                               "in self._last_lp_rows; an engine that overrides it overrides this hook as well")
+        return ops.top_logprobs(lp, self.top_logprobs_k)
+
+    def _step_top_logprobs(self, n: int):
+        """rows 0..n-1 of the list buffers <- the selection over the log-prob rows of the step just enqueued (captured or
+        eager): one launch behind it on the same stream, before the next step overwrites the rows"""
+        ops.top_logprobs(self._st.logprobs[:n], self.top_logprobs_k, out=(self._top_idx[:n], self._top_val[:n]))
 
     @staticmethod
     def _borrow_state(lm, cap: int) -> DecodeState:
@@ -535,7 +587,7 @@ class BatchGenerator:
         movers = [r for r in range(live_after, len(self._rows)) if r not in gone_set]
         holes = sorted(r for r in gone if r < live_after)
         for dst, src in zip(holes, movers):
-            for buf in (st.tok, st.pos, st.ctx, self._lp):
+            for buf in (st.tok, st.pos, st.ctx, self._lp) + ((self._top_idx, self._top_val) if self.top_logprobs_k else ()):
                 buf[dst:dst + 1].copy_(buf[src:src + 1])
             self._table[dst].copy_(self._table[src])
             self._move_row_penalties(dst, src)
@@ -574,9 +626,11 @@ class BatchGenerator:
             where = torch.cuda.stream(self._side)
         with where:
             caches, lens, tok0, lp0, state = self._prefill_requests(batch)
+            top0 = self._prefill_top_logprobs(batch) if self.top_logprobs_k else None
             ev = self._event()
             ev.record()
-        self._pending.append(_Admission(batch, caches, lens, tok0, lp0, state, ev, tic, pen=getattr(self, "_last_pen", None)))
+        self._pending.append(_Admission(batch, caches, lens, tok0, lp0, state, ev, tic, pen=getattr(self, "_last_pen", None),
+                                        top0=top0))
         self._last_pen = None
 
     def _admit_join(self) -> List[PromptProgress]:
@@ -615,6 +669,9 @@ class BatchGenerator:
                 st.ctx[r:r + 1].copy_(p.state[1, i:i + 1])
                 if p.lp0 is not None:
                     self._lp[r:r + 1].copy_(p.lp0[i:i + 1])
+                if p.top0 is not None:
+                    self._top_idx[r:r + 1].copy_(p.top0[0][i:i + 1])
+                    self._top_val[r:r + 1].copy_(p.top0[1][i:i + 1])
                 self._table[r].copy_(lm.pool.block_table[seq.seq])
                 if self.kv_bits is not None:
                     self._quantize_joined(seq)          # KVCache.to_quantized right after the prefill (stream-ordered)
@@ -644,6 +701,8 @@ class BatchGenerator:
             self._t_results = time.perf_counter()
             self._gen_time_counter += self._t_results - t_launch
             toks, lps = self._pin_tok[slot].numpy(), self._pin_lp[slot].numpy()
+            if self.top_logprobs_k:
+                top_i, top_v = self._pin_top_idx[slot].numpy(), self._pin_top_val[slot].float().numpy()
             live = {row.uid: r for r, row in enumerate(self._rows)}
             gone = []
             for i, uid in enumerate(uids):
@@ -663,7 +722,8 @@ class BatchGenerator:
                         self._force_next_token(r, int(forced))
                 if reason is not None:
                     gone.append(r)
-                responses.append(self.Response(uid, tok, float(lps[i]) if self.compute_logprobs else 0.0, reason))
+                top = list(zip(top_i[i].tolist(), top_v[i].tolist())) if self.top_logprobs_k else None
+                responses.append(self.Response(uid, tok, float(lps[i]) if self.compute_logprobs else 0.0, reason, top))
             self._gen_tokens_counter += len(responses)
             if gone:
                 self._drop_rows(gone)
@@ -693,6 +753,9 @@ class BatchGenerator:
         self._pin_tok[slot, :n].copy_(st.tok[:n], non_blocking=True)
         if self.compute_logprobs:
             self._pin_lp[slot, :n].copy_(self._lp[:n], non_blocking=True)
+        if self.top_logprobs_k:
+            self._pin_top_idx[slot, :n].copy_(self._top_idx[:n], non_blocking=True)
+            self._pin_top_val[slot, :n].copy_(self._top_val[:n], non_blocking=True)
         ev = self._event()
         ev.record()
         t_launch = time.perf_counter()
@@ -705,6 +768,8 @@ class BatchGenerator:
         self._decode_rows(width)
         if self.compute_logprobs:
             self._lp[:n].copy_(self._row_logprobs(n))
+        if self.top_logprobs_k:
+            self._step_top_logprobs(n)
         for row in self._rows:
             row.seq.offset += 1
         self._idle_steps += 1

@@ -98,6 +98,10 @@ VLM_INTERNAL int vlm_sample_greedy_advance_win(const void* logits, int ld, int B
                                                void* workspace, void* ctx, void* pos, void* out_ring, int ring_len, void* step,
                                                const void* embed, void* h, int D, int ldh, VlmWindow wn, void* stream);
 
+/* top_logprobs.hip: the K best (index, log-prob) of every row in the reference's order (value descending, the higher index first
+ * among equal values) - what vlm_sample_ex does when vlm_sampler_params.input_is_logprobs == 2 */
+VLM_INTERNAL int vlm_top_logprobs(const void* lp, int ld, int B, int V, int K, void* idx, void* val, void* stream);
+
 VLM_INTERNAL int vlm_sample_last_launches(void);   /* sample.hip: kernels the last vlm_sample / vlm_sample_advance of this thread enqueued */
 
 /* sample.hip: the sampled step's tail for the engine's captured step - vlm_sample (temperature > 0; top_p / min_p / top_k) with the

@@ -1637,6 +1637,8 @@ static int sample_ex_impl(const void* logits, int ld, int B, int V, void* logpro
 
 extern "C" int vlm_sample_ex(const void* logits, int ld, int B, int V, void* logprobs, void* scratch, int ldlp, void* tok,
                              void* workspace, const vlm_sampler_params* sp, const void* step_ptr, void* stream) {
+  // input_is_logprobs == 2 (added within ABI v8): not a sampler call - the top_k best log-probs of every row, csrc/top_logprobs.hip
+  if (sp && sp->input_is_logprobs == 2) return vlm_top_logprobs(logits, ld, B, V, sp->top_k, tok, logprobs, stream);
   return sample_ex_impl(logits, ld, B, V, logprobs, scratch, ldlp, tok, workspace, sp, step_ptr, stream, nullptr);
 }
 

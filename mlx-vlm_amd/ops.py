@@ -477,6 +477,38 @@ def sample(logits, temperature=0.0, top_p=1.0, min_p=0.0, top_k=0, seed=0, step=
     return tok, lp
 
 
+def top_logprobs(logprobs, k, ws=None, out=None):
+    """The k best entries of every row of bf16 log-probs [B, V] (any row stride >= V) as the reference's batch generator lists
+    them (ar.py:1092-1122: argsort ascending, the last k, reversed): value descending, the HIGHER index first among equal
+    values (+0.0 and -0.0 are equal).  -> (indices int32 [B, k], values bf16 [B, k] - the rows' own bits at those indices).
+    vlm_sample_ex(input_is_logprobs=2); 1 <= k <= min(64, V).  `ws`: this kernel needs no workspace - the argument is handed
+    to the entry point, which ignores it, so that a caller written against (logprobs, k, ws) keeps working should a later
+    kernel split the row over workgroups and need one.  out = (indices, values): contiguous tensors to fill instead of new
+    ones (the batch generator's per-row buffers: no allocation per step)."""
+    _dev(logprobs)
+    if logprobs.dim() != 2 or logprobs.dtype != torch.bfloat16 or logprobs.stride(1) != 1:
+        raise ValueError("top_logprobs: logprobs is a bf16 [B, V] tensor with unit column stride")
+    B, V = logprobs.shape
+    k = int(k)
+    if k > _lib.TOP_LOGPROBS_MAX_K:
+        raise NotImplementedError(f"top_logprobs: k = {k}: at most {_lib.TOP_LOGPROBS_MAX_K} entries per token are built")
+    if k < 1 or k > V:
+        raise ValueError(f"top_logprobs: k = {k} outside 1 .. min({_lib.TOP_LOGPROBS_MAX_K}, V = {V})")
+    if out is None:
+        idx = torch.empty(B, k, dtype=torch.int32, device=logprobs.device)
+        val = torch.empty(B, k, dtype=torch.bfloat16, device=logprobs.device)
+    else:
+        idx, val = out
+        _dev(idx, val)
+        if (tuple(idx.shape) != (B, k) or tuple(val.shape) != (B, k) or idx.dtype != torch.int32 or val.dtype != torch.bfloat16
+                or not idx.is_contiguous() or not val.is_contiguous()):
+            raise ValueError(f"top_logprobs: out = (int32 [{B}, {k}], bf16 [{B}, {k}]), both contiguous")
+    sp = _lib.SamplerParams(input_is_logprobs=_lib.SAMPLE_MODE_TOP_LOGPROBS, top_k=k)
+    check(_lib.lib().vlm_sample_ex(_p(logprobs), logprobs.stride(0), B, V, _p(val), None, k, _p(idx), _p(ws), sp, None, _stream()),
+          "top_logprobs")
+    return idx, val
+
+
 def sample_greedy_advance(logits, tok, ctx, pos, step, embed, h, out_ring=None, want_logprobs=True, ws=None):
     """Greedy tail of a decode step (vlm_sample_greedy_advance): tok <- argmax, ctx += 1, pos += 1, ring, step += 1,
     h <- embed[tok].  -> logprobs bf16 [B, V] or None"""
