@@ -283,7 +283,39 @@ int vlm_embed_gather(const void* ids, const void* table, void* out, int T, int D
 int vlm_scatter_image_rows(const void* src, const void* dst_rows, void* dst, int n, int D, int ld_src, int ld_dst,
                            void* stream);
 
-/* pixel_values.astype(bf16) (qwen2_vl.py:44-45) with zero padding of the row to ld_dst */
+/* pixel_values.astype(bf16) (qwen2_vl.py:44-45) with zero padding of the row to ld_dst
+ *
+ * ld_src == -1 (added within ABI v8): image mode - the rows are not cast from fp32 but MADE on the device from a raw u8 RGB
+ * image, i.e. the operation replaces the image processor's resize + rescale + normalise + patch shuffle
+ * (mlx_vlm/models/qwen3_vl/processing_qwen3_vl.py:302-354) together with the cast.  `src` is then a HOST pointer to the
+ * struct below; `dst` = bf16 [rows][ld_dst], `cols` = 3 * temporal * patch * patch (VLM_ERR_SHAPE otherwise), ld_dst >= cols,
+ * ld_dst % 8 == 0, dst 16-byte aligned (VLM_ERR_ARG otherwise), and rows row_offset .. row_offset + (rh / patch) * (rw / patch) - 1 of dst are written, all ld_dst
+ * columns of each, the ones from `cols` on as zeros; `rows` is what dst holds (VLM_ERR_ARG when the image does not fit).
+ * Launches: [horizontal pass] [vertical pass] patchify.  A pass is Pillow's 8-bit resampler (ImagingResampleHorizontal_8bpc /
+ * Vertical_8bpc of src/libImaging/Resample.c): out = clip8((2^21 + sum_i px[first + i] * coeffs[i]) >> 22), int32, arithmetic
+ * shift; horizontal first, rounded to u8, then vertical.  Its tables come from the host (Pillow's precompute_coeffs +
+ * normalize_coeffs_8bpc): coeffs int32 [out][ksize], bounds int32 [out][2] = (first source index, taps <= ksize).  A NULL
+ * coeffs pointer skips the pass, and the size along that axis must then be unchanged (VLM_ERR_SHAPE).  Source indices are
+ * clamped into the image and tap counts into ksize: a bad table gives a wrong picture, not a fault.
+ * patch == 0: the passes only - `frame` is the product; dst, rows, cols and ld_dst are ignored.
+ * Bad arguments return 1 or 2 and enqueue nothing. */
+typedef struct vlm_image_patch_args {
+  const void* src;        /* u8 [height][width][3], rows src_stride BYTES apart (>= 3 * width) */
+  int height, width;
+  long long src_stride;
+  int resized_height, resized_width; /* rh, rw: multiples of patch * merge unless patch == 0 */
+  const void* coeffs_h;   /* horizontal pass, width -> rw: int32 [rw][ksize_h]; NULL = skipped */
+  const void* bounds_h;   /* int32 [rw][2] */
+  int ksize_h;
+  const void* coeffs_v;   /* vertical pass, height -> rh: int32 [rh][ksize_v]; NULL = skipped */
+  const void* bounds_v;   /* int32 [rh][2] */
+  int ksize_v;
+  void* tmp_h;            /* u8 [height][rw][3]: the horizontal result; needed when BOTH passes run */
+  void* frame;            /* u8 [rh][rw][3]: the resized frame; needed when a pass runs */
+  const void* lut;        /* bf16 [3][256]: rescale + normalise of (channel, byte) */
+  int patch, merge, temporal; /* patch_size, spatial merge_size, temporal_patch_size (every temporal copy is written) */
+  int row_offset;         /* first row of dst this image writes: several images of one call share one matrix */
+} vlm_image_patch_args;
 int vlm_cast_f32_bf16_pad(const void* src, void* dst, int rows, int cols, int ld_src, int ld_dst, void* stream);
 
 /* decode-loop bookkeeping kept on the device (cache.py:362 offset += 1; language.py:476-509

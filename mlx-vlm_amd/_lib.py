@@ -96,6 +96,17 @@ class VitArgs(C.Structure):
                 ("uniform_segments", c_int)]
 
 
+class ImagePatchArgs(C.Structure):
+    """vlm_image_patch_args (include/vlm_hip.h): what vlm_cast_f32_bf16_pad reads through `src` when ld_src == CAST_PAD_IMAGE_MODE"""
+    _fields_ = [("src", c_void_p), ("height", c_int), ("width", c_int), ("src_stride", C.c_longlong),
+                ("resized_height", c_int), ("resized_width", c_int), ("coeffs_h", c_void_p), ("bounds_h", c_void_p),
+                ("ksize_h", c_int), ("coeffs_v", c_void_p), ("bounds_v", c_void_p), ("ksize_v", c_int), ("tmp_h", c_void_p),
+                ("frame", c_void_p), ("lut", c_void_p), ("patch", c_int), ("merge", c_int), ("temporal", c_int),
+                ("row_offset", c_int)]
+
+
+CAST_PAD_IMAGE_MODE = -1                    # vlm_cast_f32_bf16_pad's ld_src: `src` is a host vlm_image_patch_args (ABI v8)
+
 DECODE_FUSED_TAIL = 1                       # vlm_decode_args.flags
 DECODE_ACT16 = 2                            # `act` holds 16 x intermediate_size elements (tiled hand-over to the down projection)
 DECODE_WINDOW = 4                           # max_kv_size on the device: ctx = [2][B] (n, w), pos = [2][B] (p, d)

@@ -6,7 +6,8 @@
 //                         gather / where there collapses to "row dst_rows[i] of the embeddings :=
 //                         image feature row i" once the image-token positions are known on the host
 // vlm_cast_f32_bf16_pad   pixel_values.astype(weight dtype) (qwen2_vl.py:44-45) fused with the
-//                         zero padding of K = 1176 -> 1216 the patch GEMM wants
+//                         zero padding of K = 1176 -> 1216 the patch GEMM wants; ld_src == -1: the rows are made from
+//                         a raw u8 image on the device instead (image_preprocess.hip)
 // vlm_decode_advance      per-step bookkeeping of the decode loop: KVCache.offset += 1
 //                         (reference mlx_vlm/models/cache.py:362) and pos = offset + rope_delta
 //                         (language.py:476-509) kept in device memory so a step can be graph-replayed
@@ -93,6 +94,7 @@ extern "C" int vlm_scatter_image_rows(const void* src, const void* dst_rows, voi
 
 extern "C" int vlm_cast_f32_bf16_pad(const void* src, void* dst, int rows, int cols, int ld_src, int ld_dst,
                                      void* stream) {
+  if (ld_src == -1) return vlm_image_patches((const vlm_image_patch_args*)src, dst, rows, cols, ld_dst, stream);   // image mode
   if (!src || !dst || rows < 0 || cols <= 0 || ld_dst < cols) return VLM_ERR_ARG;
   if (ld_dst % 8) return VLM_ERR_SHAPE;
   if (rows == 0) return VLM_OK;

@@ -102,6 +102,10 @@ VLM_INTERNAL int vlm_sample_greedy_advance_win(const void* logits, int ld, int B
  * among equal values) - what vlm_sample_ex does when vlm_sampler_params.input_is_logprobs == 2 */
 VLM_INTERNAL int vlm_top_logprobs(const void* lp, int ld, int B, int V, int K, void* idx, void* val, void* stream);
 
+/* image_preprocess.hip: what vlm_cast_f32_bf16_pad does with ld_src == -1 (u8 image -> resized frame -> bf16 patch rows) */
+struct vlm_image_patch_args;
+VLM_INTERNAL int vlm_image_patches(const struct vlm_image_patch_args* a, void* dst, int rows, int cols, int ld_dst, void* stream);
+
 VLM_INTERNAL int vlm_sample_last_launches(void);   /* sample.hip: kernels the last vlm_sample / vlm_sample_advance of this thread enqueued */
 
 /* sample.hip: the sampled step's tail for the engine's captured step - vlm_sample (temperature > 0; top_p / min_p / top_k) with the

@@ -24,7 +24,7 @@ from typing import Any, Callable, Dict, Generator, List, Optional, Tuple, TypedD
 import numpy as np
 import torch
 
-from . import _lib, ops
+from . import _lib, image_ops, ops
 from .models import cache as cache_mod
 from .sample_utils import Sampler, make_sampler
 
@@ -716,7 +716,10 @@ def embed_requests(model, input_ids_list, pixel_values_list, grids, extras=None)
     feats_all = None
     if any(has_pix):
         grid_all = np.concatenate([np.asarray(g) for g, h in zip(grids, has_pix) if h], axis=0)
-        pv = _lib.h2d_cat([p for p, h in zip(pixel_values_list, has_pix) if h], lm.device)
+        parts = [p for p, h in zip(pixel_values_list, has_pix) if h]
+        pv = image_ops.concat_patch_matrices(parts)       # the device image processor's rows stay the patch matrix
+        if pv is None:
+            pv = _lib.h2d_cat(parts, lm.device)
         feats_all = model.vision_tower(pv, grid_all)
     foff = 0
     mm = model.config.vision_config.spatial_merge_size ** 2

@@ -55,12 +55,16 @@ class Qwen2VLImageProcessor:
     def __init__(self, patch_size: int = 14, temporal_patch_size: int = 2, merge_size: int = 2,
                  min_pixels: int = 56 * 56, max_pixels: int = 14 * 14 * 4 * 1280, do_rescale: bool = True,
                  rescale_factor: float = 1 / 255.0, do_normalize: bool = True, image_mean: Optional[List[float]] = None,
-                 image_std: Optional[List[float]] = None, **kwargs):
+                 image_std: Optional[List[float]] = None, device=None, **kwargs):
         self.patch_size, self.temporal_patch_size, self.merge_size = patch_size, temporal_patch_size, merge_size
         self.min_pixels, self.max_pixels = min_pixels, max_pixels
         self.do_rescale, self.rescale_factor, self.do_normalize = do_rescale, rescale_factor, do_normalize
         self.image_mean = image_mean or [0.5, 0.5, 0.5]
         self.image_std = image_std or [0.5, 0.5, 0.5]
+        # None: the host path below (PIL + numpy, fp32 pixel_values).  A GPU device: uint8 images are uploaded as they are
+        # and resized / patchified by the HIP kernels (_process_device); there is no CPU fallback for that choice
+        self.device = device
+        self._lut_dev = None
 
     def _process_one(self, image: np.ndarray):
         from PIL import Image
@@ -109,8 +113,55 @@ class Qwen2VLImageProcessor:
                 out[:, :, :, :, c, t] = values
         return out.reshape(gh * gw, C * tps * ps * ps)
 
+    def _device_lut(self, device):
+        """bf16 [3, 256] on the device: `_patchify_u8`'s float32 table rounded to bf16, which is what the cast of the
+        fp32 pixel_values does to each of its values (round to nearest even)"""
+        import torch
+
+        from ... import _lib
+
+        key = (str(torch.device(device)), self.do_rescale, self.rescale_factor, self.do_normalize, tuple(self.image_mean),
+               tuple(self.image_std))
+        if self._lut_dev is None or self._lut_dev[0] != key:
+            lut = self._normalise(np.broadcast_to(np.arange(256, dtype=np.float32), (3, 256)).copy(), rescale=self.do_rescale)
+            self._lut_dev = (key, _lib.h2d(torch.from_numpy(np.ascontiguousarray(lut)).to(torch.bfloat16), device))
+        return self._lut_dev[1]
+
+    def _process_device(self, arrays):
+        """uint8 [3, H, W] images -> device bf16 pixel_values [N, C * T * ps * ps], a view of the zero-padded [N, patch_k]
+        patch matrix the kernels wrote (tagged, so the vision tower takes that matrix as it is), bit-equal to the cast of
+        the host path's fp32 rows.  One pinned upload of the HWC bytes per image; all images land in one matrix."""
+        import torch
+
+        from ... import _lib, image_ops, ops
+
+        if not torch.cuda.is_available():
+            raise _lib.VlmHipError(f"Qwen2VLImageProcessor(device={self.device!r}) needs a GPU (there is no CPU fallback)")
+        ps, tps, ms = self.patch_size, self.temporal_patch_size, self.merge_size
+        sizes = []
+        for a in arrays:
+            if a.shape[0] != 3:
+                raise ValueError(f"the device image path takes RGB images, got {a.shape[0]} channels")
+            sizes.append(smart_resize(a.shape[1], a.shape[2], ps * ms, self.min_pixels, self.max_pixels))
+        patch_dim = 3 * tps * ps * ps
+        counts = [(rh // ps) * (rw // ps) for rh, rw in sizes]
+        out = torch.empty(sum(counts), image_ops.patch_k_for(patch_dim), dtype=torch.bfloat16, device=self.device)
+        lut = self._device_lut(self.device)
+        off = 0
+        for a, (rh, rw), n in zip(arrays, sizes, counts):
+            hwc = _lib.h2d(np.transpose(a, (1, 2, 0)), self.device)        # contiguous already for a PIL-decoded image
+            ops.image_patches(hwc, rh, rw, "bicubic", lut, out.shape[1], patch=ps, merge=ms, temporal=tps, out=out, row_offset=off)
+            off += n
+        thw = [[1, rh // ps, rw // ps] for rh, rw in sizes]
+        return {"pixel_values": image_ops.tag_patch_matrix(out, patch_dim), "image_grid_thw": np.array(thw, dtype=np.int64)}
+
     def __call__(self, images, **kwargs):
         ps, thw = [], []
+        if self.device is not None:
+            arrays = [im if isinstance(im, np.ndarray) and im.ndim == 3 else load_image(im) for im in images]
+            if arrays and all(a.dtype == np.uint8 for a in arrays):
+                return self._process_device(arrays)
+            images = arrays                                                # non-u8 arrays keep the host path
         for im in images:
             p, g = self._process_one(im if isinstance(im, np.ndarray) and im.ndim == 3 else load_image(im))
             ps.append(p)

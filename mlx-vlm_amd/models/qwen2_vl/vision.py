@@ -156,8 +156,9 @@ class VisionModel:
     # ------------------------------------------------------------------ forward
     def __call__(self, hidden_states: torch.Tensor, grid_thw, output_hidden_states: Optional[bool] = None):
         """hidden_states: pixel_values [N, C*T*ph*pw] (f32 or bf16, rows as the processor emits them:
-        columns ordered (C, T, ph, pw)).  -> [N / merge^2, hidden_size] bf16."""
-        from ... import ops
+        columns ordered (C, T, ph, pw)).  -> [N / merge^2, hidden_size] bf16.
+        The device image processor's pixel_values (image_ops.tag_patch_matrix) already ARE the patch matrix."""
+        from ... import image_ops, ops
 
         c = self.config
         if not hidden_states.is_cuda:
@@ -165,9 +166,12 @@ class VisionModel:
         N = hidden_states.shape[0]
         # PatchEmbed (vision.py:93-101): astype(weight dtype) + zero pad of K (the channels-last move is folded
         # into the weight, see load_weights)
-        if hidden_states.dtype != torch.float32:
-            hidden_states = hidden_states.to(torch.float32)
-        x = ops.cast_pad(hidden_states.contiguous(), self.patch_k)
+        x = image_ops.patch_matrix_of(hidden_states, self.patch_dim, self.patch_k)
+        if x is None or x.device != hidden_states.device:
+            # any other tensor, bf16 included: bf16 -> fp32 -> bf16 is lossless
+            if hidden_states.dtype != torch.float32:
+                hidden_states = hidden_states.to(torch.float32)
+            x = ops.cast_pad(hidden_states.contiguous(), self.patch_k)
         cos, sin, cu, nseg, nqb, uniform = self._tables(grid_thw)
         E, dev = c.embed_dim, self.device
         mm = c.spatial_merge_size ** 2

@@ -425,6 +425,47 @@ def cast_pad(src_f32, ld_dst):
     return out
 
 
+def image_patches(u8_hwc, rh, rw, filter="bicubic", lut=None, patch_k=0, patch=14, merge=2, temporal=2, out=None, row_offset=0,
+                  return_frame=False):
+    """Pillow-exact resize of a device u8 [H, W, 3] image (any row stride, unit strides inside a row) to (rh, rw) and the
+    Qwen2-VL patchify: rows row_offset.. of `out` (bf16 [rows, patch_k], allocated when None) receive the image's
+    (rh / patch) * (rw / patch) patch rows, columns (C, T, ph, pw) through `lut` (bf16 [3, 256]), the columns from
+    3 * temporal * patch^2 on as zeros.  vlm_cast_f32_bf16_pad's image mode (include/vlm_hip.h).  lut=None: the resize alone.
+    -> out, or (out, frame) with return_frame: the resized u8 [rh, rw, 3] frame (the input itself when nothing is resized)."""
+    from . import image_ops
+
+    _dev(u8_hwc, lut, out)
+    if u8_hwc.dim() != 3 or u8_hwc.dtype != torch.uint8 or u8_hwc.shape[2] != 3 or u8_hwc.stride(2) != 1 or u8_hwc.stride(1) != 3:
+        raise ValueError("image_patches: the image is a u8 [H, W, 3] tensor whose rows are contiguous")
+    H, W = int(u8_hwc.shape[0]), int(u8_hwc.shape[1])
+    rh, rw = int(rh), int(rw)
+    dev = u8_hwc.device
+    th, tv = image_ops.device_tables(W, rw, filter, dev), image_ops.device_tables(H, rh, filter, dev)
+    frame = torch.empty(rh, rw, 3, dtype=torch.uint8, device=dev) if (th or tv) else None
+    tmp = torch.empty(H, rw, 3, dtype=torch.uint8, device=dev) if (th and tv) else None
+    cols = 0
+    if lut is not None:
+        if lut.dtype != torch.bfloat16 or tuple(lut.shape) != (3, 256) or not lut.is_contiguous():
+            raise ValueError("image_patches: lut is a contiguous bf16 [3, 256] tensor")
+        cols = 3 * temporal * patch * patch
+        if out is None:
+            out = torch.empty(row_offset + (rh // patch) * (rw // patch), patch_k, dtype=torch.bfloat16, device=dev)
+        if out.dtype != torch.bfloat16 or out.dim() != 2 or not out.is_contiguous():
+            raise ValueError("image_patches: out is a contiguous bf16 [rows, patch_k] tensor")
+    a = _lib.ImagePatchArgs(u8_hwc.data_ptr(), H, W, u8_hwc.stride(0), rh, rw,
+                            th[0].data_ptr() if th else None, th[1].data_ptr() if th else None, th[2] if th else 0,
+                            tv[0].data_ptr() if tv else None, tv[1].data_ptr() if tv else None, tv[2] if tv else 0,
+                            tmp.data_ptr() if tmp is not None else None, frame.data_ptr() if frame is not None else None,
+                            lut.data_ptr() if lut is not None else None, patch if lut is not None else 0, merge, temporal,
+                            row_offset)
+    check(_lib.lib().vlm_cast_f32_bf16_pad(C.cast(C.pointer(a), C.c_void_p), _p(out), out.shape[0] if out is not None else 0, cols,
+                                           _lib.CAST_PAD_IMAGE_MODE, out.shape[1] if out is not None else 0, _stream()),
+          "image_patches")
+    if return_frame:
+        return out, (frame if frame is not None else u8_hwc)
+    return out
+
+
 def sample_workspace(B, device):
     # zeroed: the first 256 bytes hold the arrival ticket of the fused greedy tail (csrc/sample.hip)
     return torch.zeros(_lib.lib().vlm_sample_workspace_bytes(B), dtype=torch.uint8, device=device)

@@ -155,20 +155,28 @@ def fit_host_threads():
 
 
 def load(path_or_hf_repo: str, adapter_path=None, lazy: bool = False, revision=None, strict: bool = True, **kwargs):
-    """reference utils.py:1065-1119 -> (model, processor).  Local paths only (no network in this build)."""
+    """reference utils.py:1065-1119 -> (model, processor).  Local paths only (no network in this build).
+    image_preprocess="device" (default "host"): the Qwen2-VL image processor resizes and patchifies uint8 images on the GPU."""
+    image_preprocess = kwargs.pop("image_preprocess", "host")
     if adapter_path is not None:
         raise NotImplementedError("LoRA adapters are out of scope (SURVEY §2.1 trainer)")
     if not os.path.isdir(path_or_hf_repo):
         raise FileNotFoundError(f"{path_or_hf_repo} is not a local model directory")
     model = load_model(path_or_hf_repo, lazy=lazy, **kwargs)
-    processor = load_processor(path_or_hf_repo, model.config)
+    processor = load_processor(path_or_hf_repo, model.config, image_preprocess=image_preprocess)
     freeze_heap()
     fit_host_threads()
     return model, processor
 
 
-def load_processor(model_path: str, config):
-    """reference utils.py:1243-1276: processor with .tokenizer, .detokenizer and tokenizer.stopping_criteria."""
+def load_processor(model_path: str, config, image_preprocess: str = "host"):
+    """reference utils.py:1243-1276: processor with .tokenizer, .detokenizer and tokenizer.stopping_criteria.
+    image_preprocess: "host" (PIL + numpy, fp32 pixel_values) or "device" (HIP resize + patchify, Qwen2-VL only)."""
+    if image_preprocess not in ("host", "device"):
+        raise ValueError(f"image_preprocess is 'host' or 'device', got {image_preprocess!r}")
+    mt = str(getattr(config, "model_type", "") or "").lower()
+    if image_preprocess == "device" and MODEL_REMAPPING.get(mt, mt) != "qwen2_vl":
+        raise NotImplementedError(f"image_preprocess='device' is built for the Qwen2-VL image processor, not for {mt}")
     from transformers import AutoTokenizer
 
     from .models.qwen2_vl.processing_qwen2_vl import Qwen2VLImageProcessor, Qwen2VLProcessor
@@ -227,6 +235,8 @@ def load_processor(model_path: str, config):
         for k in ("image_mean", "image_std", "min_pixels", "max_pixels", "patch_size", "temporal_patch_size", "merge_size"):
             if k in pc:
                 ip_kwargs[k] = pc[k]
+    if image_preprocess == "device":
+        ip_kwargs["device"] = "cuda"
     proc = Qwen2VLProcessor(Qwen2VLImageProcessor(**ip_kwargs), tok)
     eos = config.eos_token_id if getattr(config, "eos_token_id", None) is not None else tok.eos_token_id
     tok.stopping_criteria = StoppingCriteria(eos if isinstance(eos, list) else [eos], tok)
