@@ -395,13 +395,17 @@ __global__ __launch_bounds__(1024) void logit_penalties_kernel(bf16_t* __restric
 // ------------------------------------------------------------------------------------------
 // General sampler: one 1024-thread workgroup per row (the row is L2 resident).
 // ------------------------------------------------------------------------------------------
+// The one uniform of every draw (gumbel_partial_kernel, topp_mask_kernel, xtc): strictly inside (0, 1).  For x >> 8 == 0xFFFFFF
+// the sum 16777215.5 is no float and rounds to 2^24: u was 1.0f once in 2^24 elements, -log(-log(u)) = +inf, and that token won
+// the Gumbel-max whatever its probability (0.9 % of the draws at V = 151,936).  That value becomes the largest float below one;
+// every other u is what it was (oracle/ops.py::hash_uniform, bit for bit).
 __device__ __forceinline__ float hash_uniform(uint32_t seed, uint32_t step, uint32_t row, uint32_t idx) {
   uint32_t x = seed ^ 0x9E3779B9u;
   x += (step + 1u) * 0x85EBCA6Bu;
   x ^= (row + 1u) * 0xC2B2AE35u;
   x += idx * 0x27D4EB2Fu;
   x ^= x >> 16; x *= 0x7FEB352Du; x ^= x >> 15; x *= 0x846CA68Bu; x ^= x >> 16;
-  return ((float)(x >> 8) + 0.5f) * (1.0f / 16777216.0f);
+  return fminf(((float)(x >> 8) + 0.5f) * (1.0f / 16777216.0f), 0x1.fffffep-1f);
 }
 
 // exclusive prefix over the 1024 threads of the block (thread order); `total` = block sum

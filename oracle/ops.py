@@ -550,10 +550,12 @@ def apply_logits_processors(logits, tokens, logit_bias=None, repetition_penalty=
 
 
 def hash_uniform(seed: int, step: int, row: int, idx: np.ndarray) -> np.ndarray:
-    """Counter-based uniform in (0,1) used by OUR categorical sampler (the MLX
+    """Counter-based uniform in the OPEN interval (0,1) used by OUR categorical sampler (the MLX
     RNG stream, sample_utils.py:385-387 mx.random.categorical, is not
     reproducible outside MLX - SURVEY.md §7.6).  32-bit mix of
-    (seed, step, row, idx); restated bit-for-bit by the HIP kernel."""
+    (seed, step, row, idx); restated bit-for-bit by the HIP kernel.
+    u = min((float32(x >> 8) + 0.5) * 2^-24, 1 - 2^-24): for x >> 8 == 0xFFFFFF the sum 16777215.5 is no float32 and
+    rounds to 2^24, i.e. u == 1.0 and a Gumbel noise of +inf - that one value is the largest float32 below one instead."""
     M = np.uint64(0xFFFFFFFF)
     x = (np.uint64(seed) ^ np.uint64(0x9E3779B9)) & M
     x = (x + (np.uint64(step) + np.uint64(1)) * np.uint64(0x85EBCA6B)) & M
@@ -564,7 +566,8 @@ def hash_uniform(seed: int, step: int, row: int, idx: np.ndarray) -> np.ndarray:
     x ^= x >> np.uint64(15)
     x = (x * np.uint64(0x846CA68B)) & M
     x ^= x >> np.uint64(16)
-    return ((x >> np.uint64(8)).astype(np.float32) + np.float32(0.5)) * np.float32(1.0 / 16777216.0)
+    u = ((x >> np.uint64(8)).astype(np.float32) + np.float32(0.5)) * np.float32(1.0 / 16777216.0)
+    return np.minimum(u, np.nextafter(np.float32(1), np.float32(0)))
 
 
 def categorical_gumbel(logprobs, temp: float, seed: int, step: int, row: int = 0):
