@@ -264,7 +264,11 @@ int vlm_attn_decode_paged_q8(const void* q, int ldq, const void* kpool16, const 
  * slots 0 .. q_start[s] + r.  All of those must be 8-bit at the launch: the caller quantises the chunk's own tokens first
  * (vlm_kv_quantize_tokens).  Later slots, stale bytes behind a trim and pages the table does not name never reach a result.
  * total_qblocks = sum_s ceil(rows_s / 64) (host).  D == 128; arithmetic as vlm_attn_decode_paged_q8 (bf16(scale), q * scale
- * and every score rounded to bf16, softmax in fp32, unnormalised probabilities rounded to bf16). */
+ * and every score rounded to bf16, softmax in fp32, unnormalised probabilities rounded to bf16).
+ * The bf16 form: ksb == NULL && vsb == NULL (both; one NULL alone is VLM_ERR_ARG).  kpool8 / vpool8 are then the BF16 pools
+ * (K [page][Hkv][D/8][64][8], V [page][Hkv][D][64 key slots]) and nothing is quantised: the chunk's own K / V must be in the
+ * pages (vlm_mrope_kvwrite).  Same segments, same masking; arithmetic of the bf16 kernels at D == 128 (fp32 scores and
+ * softmax, P fed as the hi + lo bf16 pair).  It is the attention of a warm prefix-cache admission (mlx-vlm_amd/apc.py). */
 int vlm_attn_prefill_paged_q8(const void* q, int ldq, void* out, int ldo, const void* kpool8, const void* vpool8,
                               const void* ksb, const void* vsb, const void* block_table, int max_pages, const void* seg_seq,
                               const void* cu_q, const void* q_start, int nseg, int total_qblocks, int Hq, int Hkv, int D,

@@ -26,6 +26,7 @@ _LAZY = {
     "BatchStats": ("generate", "BatchStats"),
     "PromptCacheState": ("generate", "PromptCacheState"),
     "VisionFeatureCache": ("vision_cache", "VisionFeatureCache"),
+    "APCManager": ("apc", "APCManager"),
 }
 
 

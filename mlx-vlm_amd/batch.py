@@ -102,9 +102,19 @@ class _Admission:
     done_t: Optional[float] = None # host clock when the prefill's event was first seen fired (it may WAIT for a row after that)
     pen: Any = None                # device (hist, hist_len, params, bias_idx, bias_val) of the admitted requests, or None
     top0: Any = None               # top_logprobs_k > 0: (indices [n, k], values [n, k]) of the first tokens
+    cached: Any = None             # apc_manager: tokens of each request restored from the prefix cache (PromptProgress.cached_tokens)
 
     def waiting(self) -> int:
         return sum(1 for b in self.batch[self.joined:] if b[0] not in self.removed)
+
+
+@dataclass
+class _APCPlan:
+    """What an admission reuses of one request's prompt (apc.py)."""
+    prefix_len: int                # tokens restored from the prefix cache (a multiple of PAGE; 0 = a cold request)
+    blocks: list                   # the acquired blocks of that prefix, emptied when they are released
+    extra_hash: int                # the request's image salt
+    matched_tokens: int = 0        # what the lookup matched before the length cap and the media rule
 
 
 _ADMISSION_STREAMS: Dict[int, "torch.cuda.Stream"] = {}
@@ -135,7 +145,13 @@ class BatchGenerator:
     as in the reference's batch path `quantized_kv_start` has no effect on the uniform scheme (ar.py:776-812: the batch
     caches are quantised from the first token).  `top_logprobs_k=k` (ar.py:2209; k <= 64): every Response carries the k best
     (token, log-prob) pairs of its token's log-prob row - after the logits processors, before the sampler's filters - in the
-    reference's order (ops.top_logprobs), selected by one HIP launch behind every step.  APC and speculative drafts are outside the built path and are rejected."""
+    reference's order (ops.top_logprobs), selected by one HIP launch behind every step.  `apc_manager=mgr` (ar.py:2214-2250;
+    an `apc.APCManager`): automatic prefix caching for the Qwen2-VL family - at admission every request looks up the full 64-token
+    blocks of its prompt (salted with its image); a request whose match leaves a text-only suffix is admitted WARM: the matched
+    blocks are copied into its pages, only the suffix is embedded (no ViT call) and prefilled onto them, its queries attending
+    straight over the pages (ops.attn_prefill_paged); after every admission the prompts' new full blocks are stored.  One manager
+    may serve several generators of one model; `close()` leaves it open.  Not with kv_bits.  Speculative drafts are outside the
+    built path and are rejected."""
 
     @dataclass
     class Response:
@@ -174,6 +190,15 @@ class BatchGenerator:
         if k > MAX_TOP_LOGPROBS:
             raise NotImplementedError(f"BatchGenerator: top_logprobs_k = {k}: at most {MAX_TOP_LOGPROBS} entries per token are built")
         self.top_logprobs_k = int(k)
+        # automatic prefix caching (reference ar.py:2214-2250): an apc.APCManager, possibly shared with other generators
+        self.apc_manager = kwargs.pop("apc_manager", None)
+        if self.apc_manager is not None:
+            if self.kv_bits is not None:
+                raise NotImplementedError("BatchGenerator(apc_manager=, kv_bits=): the prefix cache holds bf16 pages; cached blocks "
+                                          "of the 8-bit KV cache are not built")
+            if int(getattr(self.apc_manager, "block_size", 0)) != PAGE:
+                raise ValueError(f"BatchGenerator(apc_manager=): block_size must be {PAGE}, the KV pool's page")
+            self._apc_check_engine(model)
         if kwargs.get("max_kv_size"):
             # reference ar.py:831-834 (to_batch_cache): make_prompt_cache's RotatingKVCache has keep = 4
             raise ValueError("RotatingKVCache with keep tokens is not supported.")
@@ -272,10 +297,9 @@ class BatchGenerator:
     def _new_decode_state(self, cap: int):
         return self._borrow_state(self.lm, cap)
 
-    def _prefill_requests(self, batch):
-        """One ViT call over all images of `batch`, one varlen prefill launch, first tokens sampled on the device.
-        -> (caches, lengths, first tokens int32 [n], their log-probs f32 [n] or None, int32 [2, n] rope position /
-        context length of each request's first decode step)"""
+    def _prefill_cold(self, batch):
+        """One ViT call over all images of `batch`, one varlen prefill launch onto empty caches.
+        -> (caches, lengths, logits of the last rows [n, V], rope deltas)"""
         from .generate import embed_requests
 
         lm = self.lm
@@ -285,10 +309,98 @@ class BatchGenerator:
         extras = [{k: v for k, v in b[3].items() if k not in ("pixel_values", "image_grid_thw", _PROCS_KEY, _PYPROCS_KEY, _BUDGET_KEY)}
                   for b in batch]
         emb, pos, lens, deltas = embed_requests(self.model, ids_l, pix_l, grid_l, extras)
-        caches = [lm.make_cache() for _ in batch]
-        for c, L, b in zip(caches, lens, batch):
-            c[0]._seq.reserve(L + b[2] + 2)          # prompt + every token it may generate + the step in flight
-        logits = lm.prefill(emb, pos, caches, lens, "last")
+        caches = []
+        try:
+            for L, b in zip(lens, batch):
+                caches.append(lm.make_cache())
+                caches[-1][0]._seq.reserve(L + b[2] + 2)          # prompt + every token it may generate + the step in flight
+            logits = lm.prefill(emb, pos, caches, lens, "last")
+        except BaseException:
+            self._release_caches(caches)             # (no sequence slot or page stays with a failed admission)
+            raise
+        return caches, list(lens), logits, list(deltas)
+
+    @staticmethod
+    def _release_caches(caches):
+        for c in caches:
+            if c is not None:
+                c[0]._seq.release()
+
+    def _prefill_warm(self, batch, plans):
+        """Requests with a cached prefix (plans[i].prefix_len > 0): the matched blocks are copied into the first pages of each
+        sequence, only the SUFFIX tokens are embedded - no ViT call, no pixel upload: a usable prefix covers every image span
+        whole - and prefilled onto the pages in one launch chain, their queries attending straight over the pages
+        (ops.attn_prefill_paged).  M-RoPE positions and the rope delta come from the FULL prompt and its grid.
+        -> (caches, full prompt lengths, logits of the last rows [n, V], rope deltas)"""
+        lm = self.lm
+        caches, lens, deltas, embs, poss, sfx = [], [], [], [], [], []
+        try:
+            for b, pl in zip(batch, plans):
+                ids = np.asarray(b[1]).reshape(1, -1)
+                L, P = ids.shape[1], pl.prefix_len
+                cache = lm.make_cache()
+                seq = cache[0]._seq
+                caches.append(cache)
+                seq.reserve(L + b[2] + 2)
+                self._apc_restore(seq, pl)
+                grid = b[3].get("image_grid_thw")
+                if b[3].get("pixel_values") is not None:
+                    p, d = lm.get_rope_index(ids, np.asarray(grid), None, None)
+                else:
+                    p, d = lm.get_rope_index(ids)
+                    p = np.broadcast_to(p[None], (3,) + p.shape)
+                embs.append(lm.embed_tokens(ids[:, P:]).reshape(L - P, -1))
+                poss.append(np.asarray(p).reshape(3, -1)[:, P:])
+                sfx.append(L - P)
+                lens.append(L)
+                deltas.append(int(np.asarray(d).reshape(-1)[0]))
+            logits = lm.prefill(torch.cat(embs, dim=0), np.concatenate(poss, axis=1), caches, sfx, "last", paged_attn=True)
+        except BaseException:
+            self._release_caches(caches)
+            raise
+        return caches, lens, logits, deltas
+
+    def _prefill_logits(self, batch, plans):
+        """-> (caches, lengths, last-row logits [n, V], rope deltas) of `batch` in request order.  Without a prefix-cache hit
+        this is `_prefill_cold(batch)` - the calls and the launch of a generator without a manager; otherwise the cold and the
+        warm requests run as two prefill calls and their rows are put back in request order."""
+        warm = [i for i, pl in enumerate(plans) if pl is not None and pl.prefix_len > 0]
+        if not warm:
+            return self._prefill_cold(batch)
+        cold = [i for i in range(len(batch)) if i not in set(warm)]
+        n = len(batch)
+        caches, lens, deltas, logits = [None] * n, [0] * n, [0] * n, None
+        for idx, warm_part in ((cold, False), (warm, True)):
+            if not idx:
+                continue
+            try:
+                part = (self._prefill_warm([batch[i] for i in idx], [plans[i] for i in idx]) if warm_part
+                        else self._prefill_cold([batch[i] for i in idx]))
+            except BaseException:
+                self._release_caches(caches)         # the half that had succeeded (each half releases its own on failure)
+                raise
+            c, l, lg, d = part
+            if logits is None:
+                V = lg.shape[1]
+                logits = torch.empty(n, (V + 7) & ~7, dtype=lg.dtype, device=lg.device)[:, :V]      # pitch: see DecodeState
+            logits[h2d(np.asarray(idx, dtype=np.int64), lg.device)] = lg
+            for j, i in enumerate(idx):
+                caches[i], lens[i], deltas[i] = c[j], l[j], d[j]
+        return caches, lens, logits, deltas
+
+    def _prefill_requests(self, batch):
+        """One ViT call over all images of `batch`, one varlen prefill launch, first tokens sampled on the device (with a prefix
+        cache: see `_prefill_logits`).
+        -> (caches, lengths, first tokens int32 [n], their log-probs f32 [n] or None, int32 [2, n] rope position /
+        context length of each request's first decode step)"""
+        lm = self.lm
+        plans = self._apc_plan(batch)
+        self._last_cached = [pl.prefix_len for pl in plans] if self.apc_manager is not None else None
+        try:
+            caches, lens, logits, deltas = self._prefill_logits(batch, plans)
+        finally:
+            self._apc_release(plans)                 # (whatever a failed prefill left acquired)
+        self._apc_commit(batch, caches, plans)
         # per-request logits processors on the FIRST token (ar.py:360-364: `tokens` is the prompt there): a history of each
         # admitted prompt + its parameter rows, applied by the device pass; the same rows move into the decode state at the join
         self._last_pen = None
@@ -330,6 +442,67 @@ class BatchGenerator:
         ctx = np.asarray(lens, dtype=np.int32)
         state = h2d(np.stack([ctx + np.asarray(deltas, dtype=np.int32), ctx]), lm.device)
         return caches, list(lens), tok0, lp0, state
+
+    # ---- automatic prefix caching (apc.py).  `_apc_plan` / `_apc_restore` / `_apc_commit` are host logic + indexed copies on the
+    # pool (they run on CPU pools under a mock engine); `_apc_check_engine` is the engine's part.  Every copy they enqueue lands
+    # on the stream the admission runs on (`_admit_begin`: the side stream, or the current one) - the manager's stream invariant.
+    def _apc_check_engine(self, model):
+        """what the warm admission is built for: the Qwen2-VL family (suffix-only embedding, M-RoPE from the full prompt) on the
+        128-wide heads of ops.attn_prefill_paged"""
+        if not hasattr(model, "merge_input_ids_with_image_features"):
+            raise NotImplementedError("BatchGenerator(apc_manager=): automatic prefix caching is built for the Qwen2-VL family; "
+                                      f"{type(model).__module__} embeds its prompts through its own get_input_embeddings")
+        lm = model.language_model
+        if getattr(lm, "head_dim", 128) != 128:
+            raise NotImplementedError("BatchGenerator(apc_manager=): the paged prefill attention is built for 128-wide heads")
+
+    def _apc_plan(self, batch):
+        """Per request: look its prompt up, apply the length cap and the media rule, release what is not used.
+        -> one `_APCPlan` per request (None without a manager); the blocks of a plan with prefix_len > 0 stay acquired until
+        `_apc_restore` has enqueued their copies."""
+        mgr = self.apc_manager
+        if mgr is None:
+            return [None] * len(batch)
+        from . import apc
+
+        media = apc.media_token_ids(getattr(self.model, "config", None))
+        plans = []
+        for b in batch:
+            ids = np.asarray(b[1], dtype=np.int64).reshape(-1)
+            extra = apc.hash_image_payload(b[3].get("pixel_values"), b[3].get("image_grid_thw"))
+            blocks, matched = mgr.lookup_prefix(ids, extra)
+            prefix, why = apc.usable_prefix_len(len(ids), matched, apc.media_safe_prefix_min(ids, media), PAGE)
+            if why is not None:
+                mgr.record_reject(why, uid=b[0], matched_tokens=matched)
+            keep = prefix // PAGE
+            mgr.release(blocks[keep:])
+            plans.append(_APCPlan(prefix, list(blocks[:keep]), extra, matched))
+        return plans
+
+    def _apc_restore(self, seq, plan):
+        """the plan's blocks -> the first pages of `seq` (reserved by the caller), offset = prefix_len; the blocks are released:
+        their copies are enqueued, and an eviction can only be enqueued behind them"""
+        n = plan.prefix_len // PAGE
+        self.apc_manager.restore(plan.blocks, seq.pages[:n], self.lm.pool)
+        seq.set_offset(plan.prefix_len)
+        self._apc_release([plan])
+
+    def _apc_release(self, plans):
+        for pl in plans:
+            if pl is not None and pl.blocks:
+                self.apc_manager.release(pl.blocks)
+                pl.blocks = []
+
+    def _apc_commit(self, batch, caches, plans):
+        """after the admission's prefill is enqueued: count what was really prefilled and store every full block of the PROMPTS
+        the manager does not hold yet (generated tokens are never stored)"""
+        mgr = self.apc_manager
+        if mgr is None:
+            return
+        for b, c, pl in zip(batch, caches, plans):
+            ids = np.asarray(b[1], dtype=np.int64).reshape(-1)
+            mgr.record_served(len(ids) - pl.prefix_len)
+            mgr.store_pages(ids, c[0]._seq.pages, self.lm.pool, extra_hash=pl.extra_hash)
 
     def _decode_rows(self, width: int):
         """One decode step over rows 0..width-1 of the state: tok <- sampled token, pos and ctx advanced by one."""
@@ -630,8 +803,8 @@ class BatchGenerator:
             ev = self._event()
             ev.record()
         self._pending.append(_Admission(batch, caches, lens, tok0, lp0, state, ev, tic, pen=getattr(self, "_last_pen", None),
-                                        top0=top0))
-        self._last_pen = None
+                                        top0=top0, cached=getattr(self, "_last_cached", None)))
+        self._last_pen = self._last_cached = None
 
     def _admit_join(self) -> List[PromptProgress]:
         """Give free rows to prefilled requests, oldest admission first; an admission whose event has not fired is
@@ -681,7 +854,8 @@ class BatchGenerator:
                 self._rows.append(_Row(uid=b[0], seq=seq, max_tokens=b[2], prompt_tokens=L, procs=spec, py_procs=py,
                                        tokens=h2d(np.asarray(b[1], dtype=np.int32).reshape(-1), lm.device) if py else None,
                                        budget=b[3].get(_BUDGET_KEY)))
-                out.append(PromptProgress(uid=b[0], prompt_tokens=L, prompt_tps=L / dt if dt > 0 else 0.0, prompt_time=dt))
+                out.append(PromptProgress(uid=b[0], prompt_tokens=L, prompt_tps=L / dt if dt > 0 else 0.0, prompt_time=dt,
+                                          cached_tokens=int(p.cached[i]) if p.cached else 0))
             if p.joined >= len(p.batch):
                 self._pending.pop(0)
             elif not p.waiting():                     # only removed requests left

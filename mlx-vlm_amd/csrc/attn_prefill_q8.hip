@@ -19,6 +19,7 @@
 // are dispatched first.
 #include "attn_pagesplit.hpp"
 #include "attn_q8.hpp"
+#include "internal.h"
 #include "../../include/vlm_hip.h"
 
 namespace {
@@ -199,10 +200,14 @@ extern "C" int vlm_attn_prefill_paged_q8(const void* q, int ldq, void* out, int 
                                          const void* ksb, const void* vsb, const void* block_table, int max_pages,
                                          const void* seg_seq, const void* cu_q, const void* q_start, int nseg, int total_qblocks,
                                          int Hq, int Hkv, int D, float scale, void* stream) {
-  if (!q || !out || !kpool8 || !vpool8 || !ksb || !vsb || !block_table || !seg_seq || !cu_q || !q_start) return VLM_ERR_ARG;
+  if (!q || !out || !kpool8 || !vpool8 || !block_table || !seg_seq || !cu_q || !q_start) return VLM_ERR_ARG;
+  if ((ksb == nullptr) != (vsb == nullptr)) return VLM_ERR_ARG;      // both: the 8-bit pools; neither: the bf16 pools
   if (max_pages <= 0 || nseg <= 0 || Hq <= 0 || Hkv <= 0 || Hq % Hkv != 0 || Hq > 65535) return VLM_ERR_ARG;
   if (D != HD || ldq % 8 != 0 || ldo % 4 != 0) return VLM_ERR_SHAPE;
   if (total_qblocks <= 0) return VLM_OK;
+  if (!ksb)      // the bf16 form (attn_prefill_paged.hip): kpool8 / vpool8 are the bf16 pools
+    return vlm_attn_prefill_paged_bf16(q, ldq, out, ldo, kpool8, vpool8, block_table, max_pages, seg_seq, cu_q, q_start, nseg,
+                                       total_qblocks, Hq, Hkv, scale, stream);
   hipLaunchKernelGGL(attn_prefill_q8_kernel, dim3(total_qblocks, Hq), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)q,
                      (bf16_t*)out, (const unsigned char*)kpool8, (const unsigned char*)vpool8, (const unsigned*)ksb,
                      (const unsigned*)vsb, (const int*)block_table, (const int*)seg_seq, (const int*)cu_q, (const int*)q_start, ldq,

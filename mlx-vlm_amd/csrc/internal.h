@@ -10,6 +10,13 @@ VLM_INTERNAL int vlm_mrope_kvwrite_decode(void* qkv, int ld, int B, int Hq, int 
                                           int sec0, int sec1, const void* slot, const void* block_table, int max_pages,
                                           void* kpool, void* vpool, float qk_scale, int long_from, void* stream);
 
+// bf16 form of vlm_attn_prefill_paged_q8 (csrc/attn_prefill_paged.hip): a prompt chunk attending over the bf16 pages; the
+// arguments are checked by the exported entry (csrc/attn_prefill_q8.hip), which takes this form when ksb == vsb == NULL
+VLM_INTERNAL int vlm_attn_prefill_paged_bf16(const void* q, int ldq, void* out, int ldo, const void* kpool, const void* vpool,
+                                             const void* block_table, int max_pages, const void* seg_seq, const void* cu_q,
+                                             const void* q_start, int nseg, int total_qblocks, int Hq, int Hkv, float scale,
+                                             void* stream);
+
 // ---- skinny-M decode GEMM on the matrix cores (csrc/gemv_mfma.hip): 3 <= M <= 16 batch rows
 struct VlmRopeKv {
   const int* pos;            // [M] rope position (all three M-RoPE axes are equal for a decoded text token)

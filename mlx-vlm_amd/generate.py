@@ -122,7 +122,8 @@ class GenerateKwargs(TypedDict, total=False):
     """reference generate/types.py:20-63: the keyword arguments generate / stream_generate / generate_step accept.  The same
     names; array-typed entries are torch tensors or numpy arrays here.  Options outside the built path are accepted by the
     type and REFUSED at the call (NotImplementedError) rather than ignored: kv_key_bits / kv_value_bits / kv_*_scheme
-    (TurboQuant), apc_manager / apc_tenant (automatic prefix caching), video."""
+    (TurboQuant), video.  apc_manager / apc_tenant are accepted and IGNORED by generate / stream_generate (their prefix reuse is
+    `prompt_cache_state=`); automatic prefix caching is built for `BatchGenerator(apc_manager=)` (apc.py)."""
     max_tokens: int
     temperature: float
     repetition_penalty: Optional[float]

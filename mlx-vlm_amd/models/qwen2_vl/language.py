@@ -456,16 +456,19 @@ class LanguageModel:
 
     # ------------------------------------------------------------------ prefill over concatenated sequences
     def prefill(self, inputs_embeds: torch.Tensor, position_ids: np.ndarray, caches: List[List[KVCache]],
-                lengths: List[int], logits_rows: str = "last", reserve_extra: int = 0) -> torch.Tensor:
+                lengths: List[int], logits_rows: str = "last", reserve_extra: int = 0, paged_attn: bool = False) -> torch.Tensor:
         """inputs_embeds [T, D] (sequences concatenated, lengths[i] tokens each); position_ids int [3, T];
         caches[i] = the layer views of sequence i (appended after their current offset).
+        paged_attn: chunks onto NON-EMPTY bf16 caches attend straight over the pages (ops.attn_prefill_paged) instead of over a
+        gathered copy - the warm admission of the batch generator's prefix cache; every other caller leaves it False.
         -> logits [n_seq, V] (logits_rows == "last") or [T, V] ("all")."""
         t, dev = self.args, self.device
         T, D = inputs_embeds.shape
         hd, Hq, Hkv = self.head_dim, t.num_attention_heads, t.num_key_value_heads
         seqs = [c[0]._seq for c in caches]
         if any(s.offset != 0 for s in seqs):
-            return self._prefill_onto_cache(inputs_embeds, position_ids, caches, lengths, logits_rows, reserve_extra)
+            return self._prefill_onto_cache(inputs_embeds, position_ids, caches, lengths, logits_rows, reserve_extra,
+                                            paged_attn=paged_attn)
         cu = np.concatenate([[0], np.cumsum(lengths)]).astype(np.int32)
         kv_seq = np.concatenate([np.full(n, s.seq, dtype=np.int32) for n, s in zip(lengths, seqs)])
         kv_slot = np.concatenate([np.arange(n, dtype=np.int32) for n in lengths])
@@ -512,14 +515,17 @@ class LanguageModel:
         self._keep = (h, xn, qkv, attn, act, xlast, pos_d, meta, rows_d)  # keep alive until the stream has run
         return logits
 
-    def _prefill_onto_cache(self, inputs_embeds, position_ids, caches, lengths, logits_rows, reserve_extra):
+    def _prefill_onto_cache(self, inputs_embeds, position_ids, caches, lengths, logits_rows, reserve_extra, paged_attn=False):
         """A prompt chunk appended to a NON-EMPTY cache: chunked prefill (reference ar.py:426-472) and `prompt_cache=`
         continuation across calls, i.e. multi-turn (dispatch.py:861-882, common.py:243-263).  The chunk's queries attend
         to [cached tokens | the chunk] (cache.py:345-367 + base.py:366-373 with the causal mask offset by the cache
         length).  Kept simple: the layer loop runs here over the C-ABI operators; per layer the cached k / v rows are fetched
         back into a full-length token-major buffer (vlm_kv_gather) and the varlen causal attention runs with the segment's
         query rows starting at the cache length (vlm_attn_prefill's q_start, round 6: the prefix rows are keys only - they used
-        to carry zero queries, O(Tf^2) per chunk)."""
+        to carry zero queries, O(Tf^2) per chunk).
+        paged_attn (the warm admission of the prefix cache, batch.py: the admission path of every warm request, not a rare one):
+        no gather and no full-length buffer - the chunk's rows attend over the bf16 pages in place (ops.attn_prefill_paged, the
+        bf16 twin of the 8-bit branch below), whatever the chunk's length.  bf16 caches and 128-wide heads only."""
         if any(c[0]._seq.rotating for c in caches):
             raise NotImplementedError("max_kv_size: a multi-token update of a non-empty rotating cache (the reference first trims "
                                       "the window to max_size - 1 + S, cache.py:486-505) is not built; only the first prompt")
@@ -547,13 +553,28 @@ class LanguageModel:
         tot = [o + n for o, n in zip(offs, lengths)]
         cu_full = np.concatenate([[0], np.cumsum(tot)]).astype(np.int32)
         Tf = int(cu_full[-1])
+        pos = np.ascontiguousarray(position_ids, dtype=np.int32)
+        pos_d = _lib.h2d(pos, dev)
+        if paged_attn:
+            # no full-length buffer: what the layer loop needs is where the chunk's own K / V go and the segments of the launch
+            if q8 or hd != 128:
+                raise NotImplementedError("paged_attn: the paged prefill attention is built for bf16 caches with 128-wide heads")
+            cu_new = np.concatenate([[0], np.cumsum(lengths)]).astype(np.int32)
+            meta = _lib.h2d(np.concatenate([np.concatenate([np.full(n, s.seq, np.int32) for n, s in zip(lengths, seqs)]),
+                                            np.concatenate([o + np.arange(n, dtype=np.int32) for o, n in zip(offs, lengths)]),
+                                            cu_new, np.asarray([s.seq for s in seqs], dtype=np.int32),
+                                            np.asarray(offs, dtype=np.int32)]).astype(np.int32), dev)
+            S_ = len(seqs)
+            new_seq_d, new_slot_d = meta[:T], meta[T:2 * T]
+            pg_cu_d, pg_seq_d, pg_start_d = meta[2 * T:2 * T + S_ + 1], meta[2 * T + S_ + 1:2 * T + 2 * S_ + 1], meta[2 * T + 2 * S_ + 1:]
+            pg_nqb = int(sum((n + ops.PAGED_PREFILL_QBLOCK - 1) // ops.PAGED_PREFILL_QBLOCK for n in lengths))
+            return self._onto_cache_layers_paged(inputs_embeds, pos_d, lengths, seqs, logits_rows, new_seq_d, new_slot_d, pg_cu_d,
+                                                 pg_seq_d, pg_start_d, pg_nqb)
         # rows of the full-length buffer: per sequence [prefix | chunk]
         new_rows = np.concatenate([np.arange(cu_full[i] + offs[i], cu_full[i + 1]) for i in range(len(seqs))]).astype(np.int64)
         old_rows = np.concatenate([np.arange(cu_full[i], cu_full[i] + offs[i]) for i in range(len(seqs))]).astype(np.int64)
         full_seq = np.concatenate([np.full(tot[i], seqs[i].seq, np.int32) for i in range(len(seqs))])
         full_slot = np.concatenate([np.arange(tot[i], dtype=np.int32) for i in range(len(seqs))])
-        pos = np.ascontiguousarray(position_ids, dtype=np.int32)
-        pos_d = _lib.h2d(pos, dev)
         new_rows_d, old_rows_d = _lib.h2d(new_rows, dev), _lib.h2d(old_rows, dev)
         seq_d, slot_d, cu_d = _lib.h2d(full_seq, dev), _lib.h2d(full_slot, dev), _lib.h2d(cu_full, dev)
         new_seq_d, new_slot_d = seq_d[new_rows_d], slot_d[new_rows_d]
@@ -631,6 +652,45 @@ class LanguageModel:
             attn = ops.attn_prefill(full, full[:, Hq * hd:], full[:, (Hq + Hkv) * hd:], cu_d, nqb, Hq, Hkv, hd, scale, True,
                                     q_start=qstart_d)
             h = ops.gemm(attn[new_rows_d].contiguous(), w[f"{i}.wo"], res=h, epilogue=ops.EPI_RESIDUAL)
+            xn = ops.rmsnorm(h, w[f"{i}.ln2"], t.rms_norm_eps)
+            act = ops.gemm(xn, w[f"{i}.wgu"], epilogue=ops.EPI_SWIGLU)
+            h = ops.gemm(act, w[f"{i}.wdown"], res=h, epilogue=ops.EPI_RESIDUAL)
+        cu_new = np.concatenate([[0], np.cumsum(lengths)])
+        rows = (cu_new[1:] - 1) if logits_rows == "last" else np.arange(T)
+        xl = ops.rmsnorm(h[_lib.h2d(rows.astype(np.int64), dev)].contiguous(), self._w["norm"], t.rms_norm_eps)
+        logits = ops.gemm(xl, dense(self._w["head"]))[:, : t.vocab_size]
+        for n, s in zip(lengths, seqs):
+            s.offset += n
+        return logits
+
+    def _onto_cache_layers_paged(self, inputs_embeds, pos_d, lengths, seqs, logits_rows, new_seq_d, new_slot_d, cu_d, seg_seq_d,
+                                 q_start_d, nqb):
+        """The layer loop of `_prefill_onto_cache(paged_attn=True)`: per layer the chunk's K / V go into the pages
+        (mrope_kvwrite_) and its rows attend over [cached prefix | chunk] in place (ops.attn_prefill_paged) - no gather, no
+        full-length buffer, no row scatter.  4-bit matrices are materialised per layer as in the gather form."""
+        t, dev, pool = self.args, self.device, self.pool
+        hd, Hq, Hkv = self.head_dim, t.num_attention_heads, t.num_key_value_heads
+        bt = pool.block_table
+        T = int(sum(lengths))
+        scale = float(getattr(t, "attn_scale", 0.0) or 0.0) or hd ** -0.5
+        sec = self.mrope_section
+        h = inputs_embeds.contiguous().clone()
+
+        def dense(x):
+            return ops.dequant_w4(x.wq, x.sb) if hasattr(x, "wq") else x
+
+        inv_tab = self._w["inv_freq"][hd // 2:] if getattr(self, "_prefill_rope_long", False) else self._w["inv_freq"]
+        qk_scale = getattr(t, "rope_qk_scale", None)
+        for i in range(t.num_hidden_layers):
+            w = {k: (dense(v) if k.startswith(f"{i}.") else v) for k, v in self._w.items()
+                 if k.startswith(f"{i}.") or k in ("inv_freq", "norm")} if self.quantized else self._w
+            kp, vp = pool.kpool[i], pool.vpool[i]
+            xn = ops.rmsnorm(h, w[f"{i}.ln1"], t.rms_norm_eps)
+            qkv = ops.gemm(xn, w[f"{i}.wqkv"], bias=w[f"{i}.bqkv"], epilogue=ops.EPI_BIAS)
+            ops.mrope_kvwrite_(qkv, Hq, Hkv, hd, pos_d[0], pos_d[1], pos_d[2], inv_tab, int(sec[0]), int(sec[1]), kv_seq=new_seq_d,
+                               kv_slot=new_slot_d, block_table=bt, kpool=kp, vpool=vp, qk_scale=qk_scale)
+            attn = ops.attn_prefill_paged(qkv, kp, vp, bt, seg_seq_d, cu_d, q_start_d, nqb, Hq, Hkv, hd, scale)
+            h = ops.gemm(attn, w[f"{i}.wo"], res=h, epilogue=ops.EPI_RESIDUAL)
             xn = ops.rmsnorm(h, w[f"{i}.ln2"], t.rms_norm_eps)
             act = ops.gemm(xn, w[f"{i}.wgu"], epilogue=ops.EPI_SWIGLU)
             h = ops.gemm(act, w[f"{i}.wdown"], res=h, epilogue=ops.EPI_RESIDUAL)

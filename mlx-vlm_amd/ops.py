@@ -400,6 +400,33 @@ def attn_prefill_paged_q8(q, kpool8, vpool8, ksb, vsb, block_table, seg_seq, cu_
     return out
 
 
+PAGED_PREFILL_QBLOCK = 64   # query rows per workgroup of the bf16 form (csrc/attn_prefill_paged.hip)
+
+
+def attn_prefill_paged(q, kpool, vpool, block_table, seg_seq, cu_q, q_start, total_qblocks, Hq, Hkv, D, scale, out=None):
+    """causal attention of prompt chunk(s) straight over the BF16 paged KV pools (vlm_attn_prefill_paged_q8 with NULL scale
+    pointers: csrc/attn_prefill_paged.hip) - no kv_gather_, no full-length buffer.  Arguments as attn_prefill_paged_q8: q [T, *]
+    with data_ptr at head 0 of row 0 and stride(0) = the row stride; rows cu_q[s] .. cu_q[s + 1] - 1 belong to the sequence in
+    block-table row seg_seq[s] and sit at positions q_start[s] + r (all int32, device).  The chunk's own K / V must be in the
+    pages already (mrope_kvwrite_).  total_qblocks = sum ceil(rows_s / PAGED_PREFILL_QBLOCK).  -> bf16 [T, Hq * D]"""
+    _dev(q, kpool, vpool, block_table, seg_seq, cu_q, q_start)
+    T = q.shape[0]
+    nseg = seg_seq.numel()
+    if cu_q.numel() != nseg + 1 or q_start.numel() != nseg:
+        raise ValueError(f"attn_prefill_paged: {nseg} segments need cu_q [{nseg + 1}] and q_start [{nseg}]")
+    for t in (block_table, seg_seq, cu_q, q_start):
+        if t.dtype != torch.int32 or not t.is_contiguous():
+            raise ValueError("attn_prefill_paged: block_table / seg_seq / cu_q / q_start are contiguous int32 tensors")
+    if kpool.dtype != torch.bfloat16 or vpool.dtype != torch.bfloat16:
+        raise ValueError("attn_prefill_paged: the pools are bf16 (the 8-bit pools go through attn_prefill_paged_q8)")
+    if out is None:
+        out = torch.empty(T, Hq * D, dtype=torch.bfloat16, device=q.device)
+    check(_lib.lib().vlm_attn_prefill_paged_q8(_p(q), q.stride(0), _p(out), out.stride(0), _p(kpool), _p(vpool), None, None,
+                                               _p(block_table), block_table.shape[1], _p(seg_seq), _p(cu_q), _p(q_start), nseg,
+                                               int(total_qblocks), Hq, Hkv, D, scale, _stream()), "attn_prefill_paged")
+    return out
+
+
 def embed_gather(ids, table, out=None):
     _dev(ids, table)
     T = ids.numel()
