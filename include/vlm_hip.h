@@ -403,8 +403,14 @@ typedef struct vlm_penalty_args {
   int n_bias;
   /* per-request processors of a continuous batch (BatchGenerator.insert(..., logits_processors=), ar.py:2584-2606):
    * row_params != NULL: fp32 [B][8] on the device = {rep_penalty, rep_ctx, pres_penalty, pres_ctx, freq_penalty, freq_ctx,
-   * n_bias, 0} of row b - the scalar fields above are then ignored - and row b's bias list sits at bias_idx / bias_val +
-   * b * bias_stride.  The host rewrites the table as requests join and leave; a captured step keeps its arguments. */
+   * n_bias, W} of row b - the scalar fields above are then ignored - and row b's bias list sits at bias_idx / bias_val +
+   * b * bias_stride.  The host rewrites the table as requests join and leave; a captured step keeps its arguments.
+   * W (slot 7; 0 = none, what every caller passed before it had a meaning): row b carries a TOKEN BITMASK of W 32-bit words
+   * (constrained decoding, reference structured.py:7-36), stored in the LAST W int32 of its bias_idx row: bias_idx +
+   * b * bias_stride + (bias_stride - W); the caller keeps n_bias + W <= bias_stride.  Token t stays iff t < 32 * W and bit
+   * (t & 31) of word (t >> 5) is set; every other logit of the row becomes bf16 -inf (0xFF80) - tokens past the mask
+   * included: a tokenizer's vocabulary is usually shorter than the logits row.  Applied after the row's bias and penalties,
+   * by a launch of its own over (vocabulary chunks, rows).  An all-zero mask leaves no token: the host refuses it. */
   const void* row_params;
   int bias_stride;
 } vlm_penalty_args;

@@ -42,6 +42,7 @@ from .sample_utils import Sampler, make_sampler
 _PROCS_KEY = "__logits_processors__"     # a request's LogitsProcessors spec inside its keyword arguments
 _PYPROCS_KEY = "__py_logits_processors__"   # ... its Python callables (tokens, logits) -> logits (eager steps)
 _BUDGET_KEY = "__thinking_budget_criteria__"   # ... its ThinkingBudgetCriteria
+_MASKPROC_KEY = "__mask_logits_processor__"    # ... its mask processor (structured.py: prepare_next_token_mask), captured steps
 MAX_ROWS = 16         # default widest decode step: one N tile of the skinny-M MFMA GEMM (csrc/gemv_mfma.hip), bf16 or 4-bit weights
 WIDE_ROWS = 64        # on request (completion_batch_size > 16): WIDE steps of 32 / 64 rows on the prefill GEMMs (engine.hip decode_impl:
                       # 192.6 us per Qwen2-VL-7B layer at 32 rows, 210 at 64, against 120 per 16-row step - profiles/r03_mfma_shapes.txt)
@@ -84,6 +85,8 @@ class _Row:
     py_procs: Any = None           # its Python callables (tokens, logits) -> logits, in order (None: none)
     tokens: Any = None             # device int32 [n]: prompt + every token fed back (kept only for rows with py_procs)
     budget: Any = None             # its ThinkingBudgetCriteria (None: none)
+    mask_proc: Any = None          # its mask processor (structured.is_mask_processor; None: none)
+    mask_w: int = -1               # words of its token bitmask in slot 7 of its row of the device tables (-1: not written yet)
 
 
 @dataclass
@@ -273,6 +276,7 @@ class BatchGenerator:
         self._pending: List[_Admission] = []         # oldest first
         self._side = _admission_stream(dev) if (async_prefill and self._cuda) else None
         self._calls = 0
+        self._unpipelined_steps = 0                   # steps that waited for their input tokens on the host (a mask row was live)
         self._idle_steps = 0
         self._width = 0
 
@@ -306,7 +310,7 @@ class BatchGenerator:
         ids_l = [b[1] for b in batch]
         pix_l = [b[3].get("pixel_values") for b in batch]
         grid_l = [b[3].get("image_grid_thw") for b in batch]
-        extras = [{k: v for k, v in b[3].items() if k not in ("pixel_values", "image_grid_thw", _PROCS_KEY, _PYPROCS_KEY, _BUDGET_KEY)}
+        extras = [{k: v for k, v in b[3].items() if k not in ("pixel_values", "image_grid_thw", _PROCS_KEY, _PYPROCS_KEY, _BUDGET_KEY, _MASKPROC_KEY)}
                   for b in batch]
         emb, pos, lens, deltas = embed_requests(self.model, ids_l, pix_l, grid_l, extras)
         caches = []
@@ -394,6 +398,7 @@ class BatchGenerator:
         -> (caches, lengths, first tokens int32 [n], their log-probs f32 [n] or None, int32 [2, n] rope position /
         context length of each request's first decode step)"""
         lm = self.lm
+        masks = self._first_masks(batch)             # (host only, and first: a refused mask leaves no pages behind)
         plans = self._apc_plan(batch)
         self._last_cached = [pl.prefix_len for pl in plans] if self.apc_manager is not None else None
         try:
@@ -403,9 +408,11 @@ class BatchGenerator:
         self._apc_commit(batch, caches, plans)
         # per-request logits processors on the FIRST token (ar.py:360-364: `tokens` is the prompt there): a history of each
         # admitted prompt + its parameter rows, applied by the device pass; the same rows move into the decode state at the join
+        # a request's mask processor (structured.py) constrains the first token too: nothing consumed yet (`is_first_token`),
+        # its mask rides in the same tables (slot 7 + the words behind the bias entries) and the same launch
         self._last_pen = None
         specs = [b[3].get(_PROCS_KEY) for b in batch]
-        if any(specs):
+        if any(specs) or any(b[3].get(_MASKPROC_KEY) is not None for b in batch):
             cap = self._st.hist.shape[1]
             host_h = np.zeros((len(batch), cap), dtype=np.int32)
             host_n = np.zeros(len(batch), dtype=np.int32)
@@ -413,12 +420,12 @@ class BatchGenerator:
                 t = np.asarray(b[1], dtype=np.int64).reshape(-1)[-cap:]
                 host_h[r, :len(t)] = t
                 host_n[r] = len(t)
-            params, bidx, bval = DecodeState.pack_row_penalties(specs, cap)
+            params, bidx, bval = DecodeState.pack_row_penalties(specs, cap, self._mask_words(), masks)
             dev = lm.device
             pen = tuple(h2d(x, dev) for x in (host_h, host_n, params, bidx, bval))
             from . import _lib
             pa = _lib.PenaltyArgs(pen[0].data_ptr(), pen[1].data_ptr(), cap, 0.0, 0, 0.0, 0, 0.0, 0, pen[3].data_ptr(),
-                                  pen[4].data_ptr(), 0, pen[2].data_ptr(), DecodeState.MAX_ROW_BIAS)
+                                  pen[4].data_ptr(), 0, pen[2].data_ptr(), bidx.shape[1])
             ops.apply_logit_penalties(logits, pa)
             self._last_pen = pen
         # RNG stream of the first tokens: the sampler keys its noise on (seed, step, row, index).  Decode steps count up
@@ -429,7 +436,7 @@ class BatchGenerator:
         for r, b in enumerate(batch):                   # Python callables on the first token: `tokens` = the prompt (ar.py:1959-1970)
             for proc in b[3].get(_PYPROCS_KEY) or ():
                 tk = h2d(np.asarray(b[1], dtype=np.int32).reshape(-1), logits.device)
-                logits[r:r + 1].copy_(self._call_proc(proc, tk, logits[r:r + 1]))
+                logits[r:r + 1].copy_(self._call_proc(proc, tk, logits[r:r + 1], last_token=int(np.asarray(b[1]).reshape(-1)[-1])))
         if self._py_sampler is not None:
             _, lp = ops.sample(logits, want_logprobs=True, temperature=0.0)
             tok0 = self._call_sampler(lp)
@@ -509,12 +516,19 @@ class BatchGenerator:
         if self._py_sampler is not None or any(row.py_procs for row in self._rows):
             return self._decode_rows_eager(width)
         self.lm.decode_step_rows(self._st, width, self._table, self._sargs, use_graph=self.use_graph,
-                                 with_logprobs=self._want_rows(), row_penalties=any(row.procs for row in self._rows),
+                                 with_logprobs=self._want_rows(),
+                                 row_penalties=any(row.procs or row.mask_proc is not None for row in self._rows),
                                  q8=self.kv_bits is not None)
 
     @staticmethod
-    def _call_proc(proc, tokens, logits_row):
-        out = proc(tokens, logits_row)
+    def _call_proc(proc, tokens, logits_row, last_token=None):
+        """a Python callable on one logits row.  One that has the reference's `process_last_token(last_token, logits)` is called
+        through it, as the reference's batch step does (ar.py:1081): it keeps its own state and wants the new token only."""
+        from .structured import call_processor, is_mask_processor
+
+        if last_token is None and (hasattr(proc, "process_last_token") or is_mask_processor(proc)):
+            last_token = int(tokens[-1])
+        out = call_processor(proc, tokens, logits_row, last_token)
         if not isinstance(out, torch.Tensor):
             out = torch.as_tensor(np.asarray(out), device=logits_row.device)
         return out.to(device=logits_row.device, dtype=logits_row.dtype).reshape(1, -1)
@@ -532,7 +546,7 @@ class BatchGenerator:
         lm, st, n = self.lm, self._st, len(self._rows)
         lm.decode_forward_rows(st, width, self._table, q8=self.kv_bits is not None)
         logits = st.logits[:width]
-        if any(row.procs for row in self._rows):
+        if any(row.procs or row.mask_proc is not None for row in self._rows):
             ops.apply_logit_penalties(logits, st.row_penalty_tables(), push_tok=st.tok[:width])
         for r, row in enumerate(self._rows):
             if row.py_procs:
@@ -625,22 +639,34 @@ class BatchGenerator:
         if len(max_tokens) != len(prompts) or len(prompt_kwargs) != len(prompts) or len(logits_processors) != len(prompts):
             raise ValueError("max_tokens / prompt_kwargs / logits_processors must have one entry per prompt")
         from .sample_utils import HIST_CAP, LogitsProcessors
-        specs, pys = [], []
+        from .structured import is_mask_processor
+        specs, pys, mps = [], [], []
         for lp in logits_processors:
             items = [x for x in (lp if isinstance(lp, (list, tuple)) else [lp]) if x]
             sp = [x for x in items if isinstance(x, LogitsProcessors)]
             py = [x for x in items if not isinstance(x, LogitsProcessors)]
             if len(sp) > 1:
                 raise NotImplementedError("one make_logits_processors spec per request")
+            # a mask processor (structured.py: prepare_next_token_mask) never sees the logits: its masks go into the row's
+            # device tables and the steps stay captured.  Beside other Python callables of the same request it is one of them
+            # (the eager step calls them in the caller's order); with a Python sampler the steps are eager anyway
+            mp = [x for x in py if is_mask_processor(x)]
+            if len(mp) > 1:
+                raise NotImplementedError("one mask processor (prepare_next_token_mask) per request")
+            if mp and len(py) == 1 and self._py_sampler is None:
+                py = []
+            else:
+                mp = []
+            mps.append(mp[0] if mp else None)
             for f in py:
-                if not callable(f):
+                if not callable(f) and not is_mask_processor(f):
                     raise TypeError("logits_processors entries must be make_logits_processors specs or callables (tokens, logits) -> logits")
             if sp:
                 DecodeState.pack_row_penalties(sp, HIST_CAP)                      # validates (bias list length) before queueing
             specs.append(sp[0] if sp else None)
             pys.append(py or None)
         uids = []
-        for p, m, kw, sp, py, crit in zip(prompts, max_tokens, prompt_kwargs, specs, pys, thinking_budget_criteria):
+        for p, m, kw, sp, py, crit, mp in zip(prompts, max_tokens, prompt_kwargs, specs, pys, thinking_budget_criteria, mps):
             ids = np.asarray(p, dtype=np.int64).reshape(-1)
             if ids.size == 0:
                 raise ValueError("empty prompt")
@@ -649,6 +675,8 @@ class BatchGenerator:
                 kw[_PROCS_KEY] = sp               # travels with the request's keyword arguments (the queue item keeps its shape)
             if py:
                 kw[_PYPROCS_KEY] = py
+            if mp is not None:
+                kw[_MASKPROC_KEY] = mp
             if crit is not None:
                 kw[_BUDGET_KEY] = crit
             self._unprocessed_sequences.append((self.uid_count, ids, int(m), kw))
@@ -728,7 +756,8 @@ class BatchGenerator:
 
     # ------------------------------------------------------------------ per-row logits processors (device tables of the state)
     def _set_row_penalties(self, r: int, pen, i: int, spec):
-        """row r of the decode state <- request i of an admission (history of its prompt + its parameters), or cleared"""
+        """row r of the decode state <- request i of an admission (history of its prompt + its parameters; with a mask
+        processor also slot 7 and the words of its first mask, which every later step replaces), or cleared"""
         st = self._st
         if spec and pen is not None:
             st.row_penalty_tables()
@@ -747,6 +776,78 @@ class BatchGenerator:
             for buf in (st.hist, st.row_params, st.row_bias_idx, st.row_bias_val):
                 buf[dst].copy_(buf[src])
             st.hist_len[dst:dst + 1].copy_(st.hist_len[src:src + 1])
+
+    # ------------------------------------------------------------------ token bitmasks of the mask rows (structured.py)
+    def _finish_reason(self, row: _Row, tok: int, ahead: int = 0) -> Optional[str]:
+        """the reference's finish rules (ar.py:1313-1316) for `tok` as token number row.num_tokens + ahead of its request"""
+        return "stop" if tok in self._stop else "length" if row.num_tokens + ahead >= row.max_tokens else None
+
+    def _vocab_size(self) -> int:
+        """width of a logits row (engine hook)"""
+        return int(self._st.logits.shape[1])
+
+    def _mask_words(self) -> int:
+        return DecodeState.mask_words_of(self._vocab_size())
+
+    def _next_mask(self, proc, uid: int, token: int):
+        """the matcher of request `uid` advanced by `token` -> the int32 words of its next mask, or None: no constraint"""
+        from .structured import mask_allows_any, mask_words_of
+
+        words = proc.prepare_next_token_mask(int(token))
+        if words is None:
+            return None
+        words = mask_words_of(words, self._mask_words())
+        if not mask_allows_any(words, self._vocab_size()):
+            # the device would turn the whole row into -inf and its log-probs into NaN; the host has the words
+            raise ValueError(f"request {uid}: its mask processor allows no token for the next step (an all-zero mask)")
+        return words
+
+    def _first_masks(self, batch):
+        """per request of an admission: the words of its FIRST token's mask (nothing consumed: the processor's is_first_token
+        call; it is handed the prompt's last token), or None"""
+        out = []
+        for b in batch:
+            proc = b[3].get(_MASKPROC_KEY)
+            out.append(None if proc is None else self._next_mask(proc, b[0], int(np.asarray(b[1]).reshape(-1)[-1])))
+        return out
+
+    def _stage_masks(self, n: int, toks):
+        """toks[r]: the token row r feeds into the step about to be enqueued (host).  Every mask row's matcher consumes its
+        token; the words go right-aligned into the row's line of a pinned buffer, one stream-ordered upload puts the lines
+        into the bias_idx table behind the bias entries, and slot 7 of the rows whose word count changed is rewritten.  (The
+        pinned lines are free again: the event this step waited on was recorded behind the previous upload.)  A row whose
+        token ends its request is not advanced - the step's output for it is dropped - and runs unconstrained."""
+        st, MW = self._st, self._mask_words()
+        if getattr(self, "_pin_mask", None) is None:
+            st.row_penalty_tables()
+            self._pin_mask = torch.zeros(st.B, MW, dtype=torch.int32)
+            self._pin_w = torch.zeros(st.B, dtype=torch.float32)
+            if self._cuda:
+                self._pin_mask, self._pin_w = self._pin_mask.pin_memory(), self._pin_w.pin_memory()
+        lo, hi, changed = n, 0, False
+        for r, row in enumerate(self._rows[:n]):
+            w = 0
+            if row.mask_proc is not None:
+                words = None
+                if self._finish_reason(row, int(toks[r]), ahead=1) is None:
+                    words = self._next_mask(row.mask_proc, row.uid, int(toks[r]))
+                if words is not None:
+                    w = len(words)
+                    self._pin_mask[r, MW - w:] = torch.from_numpy(words)
+                    lo, hi = min(lo, r), r + 1
+            changed = changed or w != row.mask_w
+            row.mask_w = w
+            self._pin_w[r] = w
+        self._upload_masks(lo, hi, n if changed else 0)
+
+    def _upload_masks(self, lo: int, hi: int, n_w: int):
+        """lines lo..hi-1 of the pinned masks -> the rows' words in the device table; slot 7 of rows 0..n_w-1 (engine hook only
+        in that it touches the state's tables: it runs on CPU tensors under a mock engine)"""
+        st = self._st
+        if hi > lo:
+            st.row_bias_idx[lo:hi, st.row_bias_idx.shape[1] - self._pin_mask.shape[1]:].copy_(self._pin_mask[lo:hi], non_blocking=True)
+        if n_w:
+            st.row_params[:n_w, 7].copy_(self._pin_w[:n_w], non_blocking=True)
 
     # ------------------------------------------------------------------ membership
     def _drop_rows(self, gone: List[int]):
@@ -849,11 +950,12 @@ class BatchGenerator:
                 if self.kv_bits is not None:
                     self._quantize_joined(seq)          # KVCache.to_quantized right after the prefill (stream-ordered)
                 spec = b[3].get(_PROCS_KEY)
-                self._set_row_penalties(r, p.pen, i, spec)
+                mproc = b[3].get(_MASKPROC_KEY)
+                self._set_row_penalties(r, p.pen, i, spec or mproc is not None)
                 py = b[3].get(_PYPROCS_KEY)
                 self._rows.append(_Row(uid=b[0], seq=seq, max_tokens=b[2], prompt_tokens=L, procs=spec, py_procs=py,
                                        tokens=h2d(np.asarray(b[1], dtype=np.int32).reshape(-1), lm.device) if py else None,
-                                       budget=b[3].get(_BUDGET_KEY)))
+                                       budget=b[3].get(_BUDGET_KEY), mask_proc=mproc))
                 out.append(PromptProgress(uid=b[0], prompt_tokens=L, prompt_tps=L / dt if dt > 0 else 0.0, prompt_time=dt,
                                           cached_tokens=int(p.cached[i]) if p.cached else 0))
             if p.joined >= len(p.batch):
@@ -886,7 +988,7 @@ class BatchGenerator:
                 row = self._rows[r]
                 row.num_tokens += 1
                 tok = int(toks[i])
-                reason = "stop" if tok in self._stop else "length" if row.num_tokens >= row.max_tokens else None
+                reason = self._finish_reason(row, tok)
                 if row.budget is not None:
                     # ar.py:1306-1314,1338-1347: the criteria sees the reported token; a pending forced id REPLACES the next
                     # token of the row - already sampled by the step in flight, so the write is stream-ordered behind it
@@ -932,6 +1034,14 @@ class BatchGenerator:
             self._pin_top_val[slot, :n].copy_(self._top_val[:n], non_blocking=True)
         ev = self._event()
         ev.record()
+        if any(row.mask_proc is not None for row in self._rows):
+            # a mask row is live: this step is NOT enqueued behind the one in flight.  Its mask depends on the token that step
+            # is sampling, so: results back (the copy above), every mask row's matcher advanced on the host, the masks staged
+            # and uploaded, then the replay - the host round trip the reference pays too (its processors carry
+            # requires_immediate_decode_yield, ar.py:2709-2730).  The next next() finds the event fired and reports the tokens
+            ev.synchronize()
+            self._unpipelined_steps += 1
+            self._stage_masks(n, self._pin_tok[slot].numpy())
         t_launch = time.perf_counter()
         if self._t_results is not None:              # the loop went straight from the last step's results to this launch
             self._gen_time_counter += max(0.0, t_launch - self._t_results - self._blocked)

@@ -491,7 +491,9 @@ static int decode_impl(Llm* m, const vlm_decode_args* a, void* stream, int* laun
   }
   if (sample && a->penalties) {
     // logits processors (ar.py:360-364): the fed token joins the history, then bias / penalties on the step's logits
-    TRY(vlm_apply_logit_penalties(a->logits, VL, B, c.vocab, a->tok, a->penalties, stream)); ++n;
+    // (the per-row form adds the launch of the rows' token bitmasks)
+    TRY(vlm_apply_logit_penalties(a->logits, VL, B, c.vocab, a->tok, a->penalties, stream));
+    n += (a->penalties->row_params && a->penalties->bias_stride > 0) ? 2 : 1;
   }
   if (sample) {
     if (fused_tail) {

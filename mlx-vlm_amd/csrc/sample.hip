@@ -392,6 +392,60 @@ __global__ __launch_bounds__(1024) void logit_penalties_kernel(bf16_t* __restric
   pass(p.freq_ctx, p.freq_p, 2);
 }
 
+// Token bitmask of a constrained row (structured.py:7-36 of the reference: the matcher's packed mask of the allowed tokens) -
+// see include/vlm_hip.h::vlm_penalty_args.  Row b carries W = row_params[b][7] words of 32 bits, the LAST W int32 of its
+// bias_idx row; token t stays iff t < 32 * W and bit (t & 31) of word (t >> 5) is set, every other logit becomes bf16 -inf.
+// W == 0: the row is untouched (its blocks leave at once).  Grid = (vocabulary chunks of 2048, rows): one row is 75 workgroups
+// at V = 151,936, not one.  A thread owns 8 consecutive tokens = one byte of the mask and one 16-byte access of the row: an
+// all-ones byte touches nothing, an all-zero byte stores without loading, a mixed one rewrites the disallowed halves.  Rows
+// whose base is not 16-byte aligned and the last V % 8 tokens go one token per thread.  Nothing at or past V is written.
+constexpr int MASK_THREADS = 256, MASK_CHUNK = MASK_THREADS * 8;
+
+__global__ __launch_bounds__(MASK_THREADS) void token_mask_kernel(bf16_t* __restrict__ logits, int ld, int V,
+                                                                  const float* __restrict__ row_params,
+                                                                  const int* __restrict__ bias_idx, int bias_stride) {
+  const int b = blockIdx.y, tid = threadIdx.x;
+  const int W = min((int)row_params[(size_t)b * 8 + 7], bias_stride);
+  if (W <= 0) return;
+  const uint32_t* __restrict__ words = reinterpret_cast<const uint32_t*>(bias_idx + (size_t)b * bias_stride + (bias_stride - W));
+  bf16_t* row = logits + (size_t)b * ld;
+  const int lo = blockIdx.x * MASK_CHUNK, hi = min(V, lo + MASK_CHUNK);
+  constexpr uint32_t NINF = 0xff80u, NINF2 = 0xff80ff80u;
+  if ((reinterpret_cast<uintptr_t>(row) & 15) == 0) {
+    const int t0 = lo + tid * 8;
+    if (t0 + 8 <= hi) {
+      const int w = t0 >> 5;
+      const uint32_t m = w < W ? (words[w] >> (t0 & 31)) & 0xffu : 0u;
+      u32x4_t* p = reinterpret_cast<u32x4_t*>(row + t0);
+      if (m == 0u) {
+        const u32x4_t all = {NINF2, NINF2, NINF2, NINF2};
+        *p = all;
+      } else if (m != 0xffu) {
+        u32x4_t v = *p;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          uint32_t x = v[e];
+          if (!((m >> (2 * e)) & 1u)) x = (x & 0xffff0000u) | NINF;
+          if (!((m >> (2 * e + 1)) & 1u)) x = (x & 0x0000ffffu) | (NINF << 16);
+          v[e] = x;
+        }
+        *p = v;
+      }
+    }
+    // the tail: the last V % 8 tokens of the row (the row's last chunk only)
+    const int t = lo + ((hi - lo) & ~7) + tid;
+    if (t < hi) {
+      const int w = t >> 5;
+      if (!(w < W && ((words[w] >> (t & 31)) & 1u))) row[t] = (bf16_t)NINF;
+    }
+  } else {
+    for (int t = lo + tid; t < hi; t += MASK_THREADS) {
+      const int w = t >> 5;
+      if (!(w < W && ((words[w] >> (t & 31)) & 1u))) row[t] = (bf16_t)NINF;
+    }
+  }
+}
+
 // ------------------------------------------------------------------------------------------
 // General sampler: one 1024-thread workgroup per row (the row is L2 resident).
 // ------------------------------------------------------------------------------------------
@@ -1727,5 +1781,12 @@ extern "C" int vlm_apply_logit_penalties(void* logits, int ld, int B, int V, con
   hipLaunchKernelGGL(logit_penalties_kernel, dim3(B), dim3(1024), 0, (hipStream_t)stream, (bf16_t*)logits, ld, V,
                      (const int*)push_tok, k);
   VLM_CHECK_LAUNCH();
+  // per-row form: the rows' token bitmasks (row_params[b][7] words at the end of the row's bias_idx entries), after the bias
+  // and the penalties of the same row - the reference appends the caller's processors to the built-in ones (ar.py:303-304)
+  if (p->row_params && p->bias_stride > 0) {
+    hipLaunchKernelGGL(token_mask_kernel, dim3((V + MASK_CHUNK - 1) / MASK_CHUNK, B), dim3(MASK_THREADS), 0, (hipStream_t)stream,
+                       (bf16_t*)logits, ld, V, (const float*)p->row_params, (const int*)p->bias_idx, p->bias_stride);
+    VLM_CHECK_LAUNCH();
+  }
   return VLM_OK;
 }

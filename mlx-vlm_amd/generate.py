@@ -258,11 +258,20 @@ def generate_step(input_ids, model, pixel_values, mask, *, max_tokens: int = DEF
 
     py_procs = [p for p in (logits_processors or []) if p is not None and not isinstance(p, _Spec)]
     extra_specs = [p for p in (logits_processors or []) if isinstance(p, _Spec) and p]
-    for p in py_procs:
-        if not callable(p):
-            raise TypeError("logits_processors entries must be callables (tokens, logits) -> logits")
     if len(extra_specs) > 1:
         raise NotImplementedError("one make_logits_processors spec per request")
+    # a mask processor (structured.py: prepare_next_token_mask(last_token) -> packed words) is no reason for the eager step: its
+    # mask of every token goes into the per-row tables of the captured step (B = 1).  Beside other callables it is one of them
+    from .structured import is_mask_processor
+
+    mask_proc = None
+    if sum(1 for p in py_procs if is_mask_processor(p)) > 1:
+        raise NotImplementedError("one mask processor (prepare_next_token_mask) per request")
+    if len(py_procs) == 1 and is_mask_processor(py_procs[0]):
+        mask_proc, py_procs = py_procs[0], []
+    for p in py_procs:
+        if not callable(p) and not is_mask_processor(p):
+            raise TypeError("logits_processors entries must be callables (tokens, logits) -> logits")
     from .sample_utils import make_logits_processors
 
     # reference ar.py:290-302: the penalties / bias of generate_step as a device-side logits pass
@@ -376,13 +385,48 @@ def generate_step(input_ids, model, pixel_values, mask, *, max_tokens: int = DEF
             done += n
     logits = lm.prefill(E[done:], P[:, done:], [prompt_cache], [L - done], "last", reserve_extra=max_tokens + 2)
 
+    if eager and mask_proc is not None:          # (a Python sampler, a thinking budget, a host-planned window: a callable again)
+        mask_proc, py_procs = None, [mask_proc]
     if eager:
         yield from _generate_step_eager(lm, ids, logits, prompt_cache, f, procs, py_procs, smp, sargs, py_sampler,
                                         thinking_budget_criteria, max_tokens, return_logprobs, maybe_quantize_kv_cache, own_cache)
         return
     maybe_quantize_kv_cache()
     step0 = torch.zeros(1, dtype=torch.int32, device=logits.device)
-    if procs:
+    if mask_proc is not None:
+        # the per-row form with one row: the spec's parameters and the mask's word count in row_params[0], the words behind
+        # the bias entries; every later step rewrites the words (and slot 7 when the count changes) before its replay
+        from .models.qwen2_vl.language import DecodeState
+        from .structured import mask_allows_any, mask_words_of
+
+        pst = lm.decode_state(1)
+        pst.set_history([ids.reshape(-1)])
+        pen_rows = pst.row_penalty_tables()
+        V, MW = logits.shape[-1], pst.mask_words
+        pin_words = torch.zeros(MW, dtype=torch.int32).pin_memory()
+        mask_w = [-1]
+
+        def stage_mask(last_token: int):
+            words = mask_proc.prepare_next_token_mask(int(last_token))
+            w = 0
+            if words is not None:
+                words = mask_words_of(words, MW)
+                if not mask_allows_any(words, V):
+                    raise ValueError("the mask processor allows no token for the next step (an all-zero mask)")
+                w = len(words)
+                pin_words[MW - w:] = torch.from_numpy(words)
+                pst.row_bias_idx[0, pst.bias_stride - MW:].copy_(pin_words, non_blocking=True)
+            if w != mask_w[0]:
+                mask_w[0] = w
+                pst.row_params[0, 7:8].copy_(_lib_h2d(np.asarray([w], dtype=np.float32), logits.device))
+
+        params, bidx, bval = DecodeState.pack_row_penalties([procs if procs else None], pst.hist.shape[1], MW)
+        pst.row_params[:1].copy_(_lib_h2d(params, logits.device))
+        pst.row_bias_idx[:1].copy_(_lib_h2d(bidx, logits.device))
+        pst.row_bias_val[:1].copy_(_lib_h2d(bval, logits.device))
+        stage_mask(int(ids.reshape(-1)[-1]))           # the first token: nothing consumed (the processor's is_first_token call)
+        ops.apply_logit_penalties(logits, pen_rows)
+    elif procs:
         # ar.py:360-364: at the first step `tokens` is the prompt; the history then grows by every token fed back (the
         # decode step pushes its input token before it applies the processors)
         pst = lm.decode_state(1)
@@ -409,11 +453,21 @@ def generate_step(input_ids, model, pixel_values, mask, *, max_tokens: int = DEF
     issued = 0   # decode steps enqueued; step s (0-based) produces generated token s + 1
     n = 0        # tokens handed to the caller (counted BEFORE the yield: a consumer that closes the generator at the
                  # yield - the stop-token path of stream_generate - has received that token)
+    if mask_proc is not None:
+        # the mask of token s + 1 needs token s on the host (the matcher consumes it): no step is enqueued ahead of the
+        # consumer - results back, matcher, upload, replay, the round trip the reference pays too
+        lookahead = 1
+    penalties = "rows" if mask_proc is not None else procs if procs else None
     try:
         while n < max_tokens:
             while issued < min(n + lookahead, max_tokens - 1):
+                if mask_proc is not None:
+                    if issued >= n:
+                        break                      # the token this step feeds goes to the caller first: a caller that stops
+                                                   # at it (a stop token) has not advanced the matcher past the end
+                    stage_mask(int(pipe.get(issued)[0]))
                 maybe_quantize_kv_cache()          # (the forward just enqueued may have carried the cache past the start)
-                lm.decode_run(st, 1, sargs, use_graph=use_graph, penalties=procs if procs else None)
+                lm.decode_run(st, 1, sargs, use_graph=use_graph, penalties=penalties)
                 issued += 1
                 pipe.push(issued, st.tok)
                 if return_logprobs:
@@ -445,6 +499,8 @@ def _generate_step_eager(lm, ids, logits, prompt_cache, f, procs, py_procs, smp,
     seq = prompt_cache[0]._seq
     dev = logits.device
     lm._rope_deltas = np.asarray(f.rope_deltas).reshape(-1, 1)[:1]
+    from .structured import call_processor
+
     need_tokens = bool(py_procs)
     tokens = _lib_h2d(np.asarray(ids, dtype=np.int32).reshape(-1), dev) if need_tokens else None
     pst = None
@@ -453,6 +509,7 @@ def _generate_step_eager(lm, ids, logits, prompt_cache, f, procs, py_procs, smp,
         pst.set_history([np.asarray(ids).reshape(-1)])
     step = torch.zeros(1, dtype=torch.int32, device=dev)
     fed: Optional[torch.Tensor] = None          # the token fed by the forward that produced `logits` (None: the prompt)
+    last_host = int(np.asarray(ids).reshape(-1)[-1])      # ... on the host: the last token of the context the processors see
     n = 0
     try:
         while n < max_tokens:
@@ -460,7 +517,7 @@ def _generate_step_eager(lm, ids, logits, prompt_cache, f, procs, py_procs, smp,
             if procs:
                 ops.apply_logit_penalties(logits, pst.penalty_args(procs), push_tok=fed)
             for proc in py_procs:
-                out = proc(tokens, logits)
+                out = call_processor(proc, tokens, logits, last_host)      # (process_last_token where the callable has it)
                 if not isinstance(out, torch.Tensor):
                     out = torch.as_tensor(np.asarray(out), device=dev)
                 logits = out.to(device=dev, dtype=logits.dtype).reshape(1, -1).contiguous()
@@ -483,6 +540,7 @@ def _generate_step_eager(lm, ids, logits, prompt_cache, f, procs, py_procs, smp,
             if n >= max_tokens:
                 break
             fed = _lib_h2d(np.asarray([y], dtype=np.int32), dev)
+            last_host = y
             if need_tokens:
                 tokens = torch.cat([tokens, fed])
             logits = lm(np.array([[y]], dtype=np.int64), cache=prompt_cache).logits[:, -1, :]

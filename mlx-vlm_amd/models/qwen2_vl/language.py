@@ -81,27 +81,46 @@ class DecodeState:
 
     MAX_ROW_BIAS = 64           # logit_bias entries per request in the per-row form
 
+    @staticmethod
+    def mask_words_of(vocab: int) -> int:
+        """32-bit words of a token bitmask over `vocab` logits"""
+        return (int(vocab) + 31) // 32
+
+    @property
+    def mask_words(self) -> int:
+        return self.mask_words_of(self.logits.shape[1])
+
+    @property
+    def bias_stride(self) -> int:
+        """entries of one row of the bias tables: the bias list in front, the row's token bitmask at the END (vlm_penalty_args)"""
+        return self.MAX_ROW_BIAS + self.mask_words
+
     def row_penalty_tables(self):
         """Device tables of the per-request processors of a continuous batch (vlm_penalty_args.row_params): fp32 [B, 8]
-        parameters and [B, MAX_ROW_BIAS] bias lists, allocated on first use, all zero = every row passes through."""
+        parameters and [B, MAX_ROW_BIAS + ceil(vocab / 32)] bias lists - wide enough for a full token bitmask behind the bias
+        entries from the start, so that a captured step never sees the pointers move - allocated on first use, all zero =
+        every row passes through."""
         if getattr(self, "row_params", None) is None:
             dev = self.hist.device
             self.row_params = torch.zeros(self.B, 8, dtype=torch.float32, device=dev)
-            self.row_bias_idx = torch.zeros(self.B, self.MAX_ROW_BIAS, dtype=torch.int32, device=dev)
-            self.row_bias_val = torch.zeros(self.B, self.MAX_ROW_BIAS, dtype=torch.float32, device=dev)
+            self.row_bias_idx = torch.zeros(self.B, self.bias_stride, dtype=torch.int32, device=dev)
+            self.row_bias_val = torch.zeros(self.B, self.bias_stride, dtype=torch.float32, device=dev)
             self._pen_rows = _lib.PenaltyArgs(self.hist.data_ptr(), self.hist_len.data_ptr(), self.hist.shape[1], 0.0, 0, 0.0, 0,
                                               0.0, 0, self.row_bias_idx.data_ptr(), self.row_bias_val.data_ptr(), 0,
-                                              self.row_params.data_ptr(), self.MAX_ROW_BIAS)
+                                              self.row_params.data_ptr(), self.bias_stride)
         return self._pen_rows
 
     @classmethod
-    def pack_row_penalties(cls, specs, hist_cap: int):
+    def pack_row_penalties(cls, specs, hist_cap: int, mask_words: int = 0, masks=None):
         """specs: one sample_utils.LogitsProcessors (or None) per row -> host arrays (params f32 [n, 8], bias_idx i32
-        [n, MAX_ROW_BIAS], bias_val f32 [n, MAX_ROW_BIAS]) in the layout of vlm_penalty_args.row_params"""
+        [n, S], bias_val f32 [n, S]; S = MAX_ROW_BIAS + mask_words) in the layout of vlm_penalty_args.row_params.
+        masks: per row None or the int32 words of its token bitmask (at most mask_words of them): they go to the end of the
+        row's bias_idx entries and their count into slot 7."""
         n = len(specs)
+        S = cls.MAX_ROW_BIAS + int(mask_words)
         params = np.zeros((n, 8), dtype=np.float32)
-        bidx = np.zeros((n, cls.MAX_ROW_BIAS), dtype=np.int32)
-        bval = np.zeros((n, cls.MAX_ROW_BIAS), dtype=np.float32)
+        bidx = np.zeros((n, S), dtype=np.int32)
+        bval = np.zeros((n, S), dtype=np.float32)
         for r, sp in enumerate(specs):
             if not sp:
                 continue
@@ -113,6 +132,15 @@ class DecodeState:
             params[r, 6] = len(bias)
             bidx[r, :len(bias)] = list(bias.keys())
             bval[r, :len(bias)] = list(bias.values())
+        for r, words in enumerate(masks or ()):
+            if words is None:
+                continue
+            from ...structured import mask_words_of
+
+            w = mask_words_of(words, mask_words)
+            if len(w):
+                params[r, 7] = len(w)
+                bidx[r, S - len(w):] = w
         return params, bidx, bval
 
     def penalty_args(self, spec):
@@ -908,7 +936,8 @@ class LanguageModel:
         return _lib.KvPool(pool.kpool.data_ptr(), pool.vpool.data_ptr(), pool.layer_stride, bt.data_ptr(), pool.max_pages, *q)
 
     def decode_run(self, st: DecodeState, n_steps: int, sampler_args: dict, use_graph: bool = True, penalties=None):
-        """Enqueue n_steps decode steps (graph replays when use_graph).  penalties: sample_utils.LogitsProcessors."""
+        """Enqueue n_steps decode steps (graph replays when use_graph).  penalties: sample_utils.LogitsProcessors, or "rows":
+        the state's per-row tables (row_penalty_tables - what a token bitmask travels in)."""
         L = _lib.lib()
         if st.window is None and any(s.rotating for s in st.seqs):
             raise NotImplementedError("max_kv_size: the captured step writes at slot = tokens seen; a rotating window runs "
@@ -929,7 +958,8 @@ class LanguageModel:
         if os.environ.get("VLM_NO_GRAPH"):           # diagnostics: every launch of the step visible to the HIP runtime's log
             use_graph = False
         if use_graph:
-            key = (st.seq_row0, st.nsplit, fused, q8, st.window, penalties.key() if penalties else None,
+            key = (st.seq_row0, st.nsplit, fused, q8, st.window,
+                   penalties if isinstance(penalties, str) else penalties.key() if penalties else None,
                    tuple(sorted(sampler_args.items())))
             if st.graph_key != key or getattr(self, "_graph_owner", None) is not st:
                 check(L.vlm_llm_decode_graph_build(self._handle, C.byref(args), stream), "decode_graph_build")

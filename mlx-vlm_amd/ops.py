@@ -602,6 +602,46 @@ def apply_logit_penalties(logits, pen_args, push_tok=None):
     return logits
 
 
+def apply_token_mask(logits, mask_words):
+    """In place on logits bf16 [B, V] (or [V]): every token whose bit is not set in its row's packed mask becomes -inf (the
+    reference's mlx_vlm_llguidance_mask, structured.py:7-36; tokens past the mask are disallowed).  mask_words: int32 [B, W]
+    (or [W] for one row; bit t & 31 of word t >> 5 = token t) as a host array or a tensor on either side.  The mask travels as
+    the per-row form of vlm_apply_logit_penalties with nothing else switched on (vlm_penalty_args: slot 7 = W, the words as the
+    row's bias_idx entries) - the launch a captured step applies its rows' masks with."""
+    import numpy as np
+
+    _dev(logits)
+    if logits.dtype != torch.bfloat16 or logits.dim() not in (1, 2) or logits.stride(-1) != 1:
+        raise ValueError("apply_token_mask: logits is a bf16 [B, V] or [V] tensor with unit column stride")
+    rows = logits if logits.dim() == 2 else logits[None]
+    B, V = rows.shape
+    if isinstance(mask_words, torch.Tensor):
+        words = mask_words
+        if words.dtype != torch.int32:
+            raise ValueError("apply_token_mask: mask_words holds int32 words")
+    else:
+        words = np.asarray(mask_words)
+        if words.dtype.kind not in "iu" or words.dtype.itemsize != 4:
+            raise ValueError("apply_token_mask: mask_words holds int32 words")
+        words = words.view(np.int32)
+    words = words.reshape(1, -1) if words.ndim == 1 else words
+    if words.ndim != 2 or words.shape[0] != B:
+        raise ValueError(f"apply_token_mask: {tuple(words.shape)} mask words for {B} rows of logits")
+    W = int(words.shape[1])
+    if W == 0:
+        rows.fill_(float("-inf"))                # no word: no token is allowed (the rule above; W = 0 in slot 7 means "no mask")
+        return logits
+    words = _lib.h2d(words, logits.device).contiguous()
+    params = torch.zeros(B, 8, dtype=torch.float32, device=logits.device)
+    params[:, 7] = W
+    zeros = torch.zeros(2, B, dtype=torch.int32, device=logits.device)          # an empty history: rings of one entry, counts
+    # (bias_val is never read with n_bias == 0; the entry point wants it non-NULL beside bias_idx)
+    pa = _lib.PenaltyArgs(zeros[0].data_ptr(), zeros[1].data_ptr(), 1, 0.0, 0, 0.0, 0, 0.0, 0, words.data_ptr(),
+                          words.data_ptr(), 0, params.data_ptr(), W)
+    apply_logit_penalties(rows, pa)
+    return logits
+
+
 def gemv_w4(x, wq, sb, bias=None, res=None, norm_w=None, out=None, eps=1e-6, epilogue=EPI_NONE):
     """decode GEMV over MLX 4-bit weights: wq int32 [N, K/8] (uint32 words), sb int32 [N, K/64] (scale | bias << 16)"""
     _dev(x, wq, sb, bias, res, norm_w, out)
