@@ -550,6 +550,11 @@ typedef struct vlm_decode_args {
                                    B in {1, 2, 4, 8}, bf16 pools (8-bit pools: argument error), one rope table
                                    (vlm_llm_config.rope_long_from > 0: argument error - that epilogue reads ctx as the offset).
                                    A bit added within ABI v8: callers that pass [B] arrays never set it. */
+#define VLM_DECODE_HOST_RING 8  /* out_ring is host-visible pinned memory (hipHostMalloc; the pointer as the device sees it): the
+                                   step's tail writes its ring entry with a system-scope vector store, so the host reads slot
+                                   step % ring_len once the step has completed (an event behind it) and no device-to-host copy is
+                                   enqueued between two steps.  The host must have read a slot before the step ring_len later is
+                                   enqueued.  Same tokens; part of the graph key like every flag.  A bit added within ABI v8. */
 
 int vlm_llm_create(const vlm_llm_config* cfg, void** handle);          /* (host) */
 int vlm_llm_destroy(void* handle);
@@ -578,7 +583,18 @@ int vlm_llm_decode_launches(void* handle);
                                        the caller asked for a split, i.e. a long context); 0 = the round-2 forms (one workgroup
                                        per pair, or split-K partials merged in the o_proj prologue) - A/B knob */
 #define VLM_TUNE_GEMV_VARIANT 8     /* A/B knob of the batch-1 GEMV launch shapes (bit 0: down projection with 6 rows per
-                                       workgroup = one workgroup per CU at N = 1536; bit 1: 3 rows) */
+                                       workgroup = one workgroup per CU at N = 1536; bit 1: 3 rows;
+                                       bit 2 (4): gate/up (RMSNorm prologue, SwiGLU, N >= 8192) with 2 rows per wave instead of 4
+                                       - twice the workgroups, a gate / up pair stays in one wave;
+                                       bit 3 (8): the head GEMV (RMSNorm prologue, no epilogue, N >= 8192) likewise;
+                                       bit 4 (16): the o_proj that merges the page-split attention (vlm_gemv_attn_out_bf16,
+                                       Hq * D <= 1536) with 4 rows per wave - half as many workgroups repeat the merge;
+                                       bit 5 (32): RMSNorm-prologue GEMVs of ONE row: the three waves of a workgroup that do not
+                                       store the normalised row fetch x / norm_w through a zero-extent buffer resource, i.e.
+                                       generate no memory traffic for them.
+                                       A row's sum does not depend on the rows its wave owns: every bit gives the same bytes.
+                                       Measured (profiles/decode_slack_ab.txt): bits 0, 2, 3 win - the Python layer sets 13 -
+                                       bit 4 loses 1.7 %, bit 5 changes nothing) */
 #define VLM_TUNE_ATTN_MERGE 9       /* where the page-split attention of a ONE-row step is merged: 1 (default) = in the o_proj
                                        GEMV's prologue (partial-only attention launch, vlm_gemv_attn_out_bf16; needs bf16 Wo,
                                        Hq * D <= 2048, <= 16 splits), 0 = by the attention launch's last-arriving workgroup */

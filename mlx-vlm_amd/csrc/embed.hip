@@ -60,7 +60,7 @@ __global__ void decode_advance_kernel(int* __restrict__ ctx, int* __restrict__ p
   const int s = *step;
   if (b < B) {
     vlm_window_advance(ctx, pos, B, b, wn);
-    if (out_ring) out_ring[(size_t)(s % ring_len) * B + b] = tok[b];
+    if (out_ring) vlm_ring_store(out_ring, (size_t)(s % ring_len) * B + b, tok[b], wn);
   }
   __syncthreads();
   if (b == 0) *step = s + 1;

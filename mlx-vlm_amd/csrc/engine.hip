@@ -83,7 +83,8 @@ inline bool same_pen(const vlm_penalty_args& x, const vlm_penalty_args* y) {
 
 // the window a step with these flags runs under ({0, 0, 0}: none)
 inline VlmWindow window_of(const Tuning& t, int flags) {
-  return (flags & VLM_DECODE_WINDOW) ? VlmWindow{t.win_size, t.win_keep, t.win_ring_pos} : VlmWindow{0, 0, 0};
+  const int host_ring = (flags & VLM_DECODE_HOST_RING) ? 1 : 0;
+  return (flags & VLM_DECODE_WINDOW) ? VlmWindow{t.win_size, t.win_keep, t.win_ring_pos, host_ring} : VlmWindow{0, 0, 0, host_ring};
 }
 
 inline bool same_key(const DecodeGraph& g, const vlm_decode_args& a, const vlm_kv_pool& kv, const VlmWindow& wn) {

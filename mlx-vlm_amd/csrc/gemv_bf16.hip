@@ -31,7 +31,11 @@
 
 namespace {
 
-enum { PRO_NONE = 0, PRO_RMSNORM = 1, PRO_ATTN = 2, PRO_ATTN_PS = 3 };
+// PRO_RMSNORM_1W (MB == 1, variant bit 5): PRO_RMSNORM whose waves 1..3 - which normalise the row again and store nothing -
+// fetch x and norm_w through a buffer resource of ZERO extent: their loads are out of range, return zeros and reach no cache
+// (measured: the duplicate loads were free, no effect on the step - profiles/decode_slack_ab.txt; A/B only)
+enum { PRO_NONE = 0, PRO_RMSNORM = 1, PRO_ATTN = 2, PRO_ATTN_PS = 3, PRO_RMSNORM_1W = 4 };
+constexpr bool is_norm(int pro) { return pro == PRO_RMSNORM || pro == PRO_RMSNORM_1W; }
 constexpr int EPI_ROPE_KV = 1 << 10;   // internal epilogue id (qkv projection)
 
 struct RopeKvArgs {
@@ -112,6 +116,20 @@ __global__ __launch_bounds__(256) void gemv_rowwave_kernel(const bf16_t* __restr
   //      wave.  The prologue then only waits for its own (oldest) loads while the weights keep streaming.
   u32x4_t xv[KC], xv2[MB > 4 ? KC : 1];
   uint4 nwv[KC];
+  if (PRO == PRO_RMSNORM_1W) {
+    // straight-line like the form below (same loads, same order, same counted waits): the extent is a wave-uniform select
+    static_assert(PRO != PRO_RMSNORM_1W || MB == 1, "one batch row");
+    const int wave_u = __builtin_amdgcn_readfirstlane(wave);
+    const int ext = wave_u < MB ? K * 2 : 0;          // bytes of x / norm_w this wave may read
+    const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(x), 0, ext, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rn = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(norm_w), 0, ext, 0x00020000);
+#pragma unroll
+    for (int c = 0; c < KC; ++c) {
+      const int chc = min(lane + 64 * c, nchunk - 1);
+      xv[c] = __builtin_bit_cast(u32x4_t, __builtin_amdgcn_raw_buffer_load_b128(rx, chc * 16, 0, 0));   // masked at use
+      nwv[c] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(rn, chc * 16, 0, 0));
+    }
+  }
   if (PRO == PRO_RMSNORM) {
 #pragma unroll
     for (int c = 0; c < KC; ++c) {
@@ -206,7 +224,7 @@ __global__ __launch_bounds__(256) void gemv_rowwave_kernel(const bf16_t* __restr
   __builtin_amdgcn_sched_barrier(0);
 
   // ---- prologue: activation vector(s) -> LDS as bf16
-  if (PRO == PRO_RMSNORM) {
+  if (is_norm(PRO)) {
     // every wave normalises row (wave % MB) - straight-line code, so the x loads above stay ahead of the
     // weight loads and get a counted wait; waves >= MB duplicate the (tiny) work and just do not store
 #pragma unroll
@@ -504,10 +522,22 @@ int launch_rw(const Args& a, int n_waves) {
   return launch_err();
 }
 
+int g_gemv_variant = 0;   // A/B bits (VLM_TUNE_GEMV_VARIANT, include/vlm_hip.h)
+
 template <int KC, int MB, int PRO, int EPI>
 int launch_rw_r(const Args& a) {
   // R = 4 rows per wave once there are enough rows to give every CU several workgroups
-  if (EPI != EPI_ROPE_KV && a.N >= 8192 && KC <= 3) return launch_rw<4, KC, MB, PRO, EPI>(a, vlm_cdiv(a.N, 4));
+  if (EPI != EPI_ROPE_KV && a.N >= 8192 && KC <= 3) {
+    // one batch row: twice the workgroups at 2 rows per wave (an interleaved gate / up pair stays in one wave) - a 55 MB
+    // launch wants ~2048 workgroups in flight (profiles/r02_hbm_ceiling.txt); gate/up 10.55 -> 10.05 us, head 67.9 -> 65.6
+    if constexpr (MB == 1 && is_norm(PRO) && (EPI == VLM_EPI_SWIGLU || EPI == VLM_EPI_NONE))
+      if (g_gemv_variant & (EPI == VLM_EPI_SWIGLU ? 4 : 8)) return launch_rw<2, KC, MB, PRO, EPI>(a, vlm_cdiv(a.N, 2));
+    return launch_rw<4, KC, MB, PRO, EPI>(a, vlm_cdiv(a.N, 4));
+  }
+  // the split merge of the o_proj prologue is repeated by every workgroup: half as many of them at 4 rows per wave
+  // (measured: 96 workgroups on 256 CUs lose 0.5 us per launch - profiles/decode_slack_ab.txt; A/B only)
+  if constexpr (PRO == PRO_ATTN_PS && KC <= 3)
+    if (g_gemv_variant & 16) return launch_rw<4, KC, MB, PRO, EPI>(a, vlm_cdiv(a.N, 4));
   if (EPI == EPI_ROPE_KV) {
     const int waves = (a.rk.Hq + a.rk.Hkv) * (a.rk.D / 2) + a.rk.Hkv * a.rk.D / 2;
     return launch_rw<2, KC, MB, PRO, EPI>(a, waves);
@@ -519,7 +549,7 @@ template <int MB, int PRO, int EPI>
 int launch_rw_k(const Args& a) {
   if (a.K <= 512 * 3) return launch_rw_r<3, MB, PRO, EPI>(a);
   if (a.K <= 512 * 7) return launch_rw_r<7, MB, PRO, EPI>(a);
-  if constexpr (PRO == PRO_RMSNORM)      // hidden 4096 (Mistral-7B / Idefics2-8B): the norm-prologue forms only
+  if constexpr (is_norm(PRO))            // hidden 4096 (Mistral-7B / Idefics2-8B): the norm-prologue forms only
     if (a.K <= 512 * 8) return launch_rw_r<8, MB, PRO, EPI>(a);
   return VLM_ERR_SHAPE;
 }
@@ -527,7 +557,10 @@ int launch_rw_k(const Args& a) {
 template <int PRO, int EPI>
 int launch_rw_m(int M, const Args& a) {
   switch (M) {
-    case 1: return launch_rw_k<1, PRO, EPI>(a);
+    case 1:
+      if constexpr (PRO == PRO_RMSNORM)
+        if (g_gemv_variant & 32) return launch_rw_k<1, PRO_RMSNORM_1W, EPI>(a);
+      return launch_rw_k<1, PRO, EPI>(a);
     case 2: return launch_rw_k<2, PRO, EPI>(a);
     case 4: return launch_rw_k<4, PRO, EPI>(a);
     case 8: return launch_rw_k<8, PRO, EPI>(a);
@@ -542,8 +575,6 @@ int launch_sk(const Args& a) {
                      a.ldy, a.ldres);
   return launch_err();
 }
-
-int g_gemv_variant = 0;   // A/B bits (VLM_TUNE_GEMV_VARIANT)
 
 template <int MB, int EPI>
 int launch_sk_k(const Args& a) {

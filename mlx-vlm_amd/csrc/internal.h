@@ -84,7 +84,14 @@ VLM_INTERNAL int vlm_gemv_mfma_rows_try(const void* xt, const void* W, const voi
 // models/cache.py::window_step (tests/test_window_rule_cpu.py pins both to the reference's RotatingKVCache)
 struct VlmWindow {
   int M, K, ring_pos;
+  int host_ring;   // VLM_DECODE_HOST_RING: out_ring is pinned host memory (travels with the window: both are options of the tails)
 };
+// the tail's token-ring entry.  A host-visible ring gets a system-scope vector store: written through to the host at once, so
+// the token is there when the step's completion is - no copy launch behind the step
+__device__ __forceinline__ void vlm_ring_store(int* ring, size_t i, int v, const VlmWindow wn) {
+  if (wn.host_ring) __hip_atomic_store(ring + i, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  else ring[i] = v;
+}
 __device__ __forceinline__ void vlm_window_advance(int* ctx, int* pos, int B, int b, const VlmWindow wn) {
   if (wn.M <= 0) {
     ctx[b] += 1;

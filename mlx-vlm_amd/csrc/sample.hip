@@ -170,7 +170,7 @@ __global__ __launch_bounds__(256) void argmax_final_advance_kernel(const float* 
     const int y = s_tok[tid];
     tok[tid] = y;
     vlm_window_advance(t.ctx, t.pos, B, tid, t.wn);
-    if (t.out_ring) t.out_ring[(size_t)(st % t.ring_len) * B + tid] = y;
+    if (t.out_ring) vlm_ring_store(t.out_ring, (size_t)(st % t.ring_len) * B + tid, y, t.wn);
   }
   gather_rows_256(t.embed, t.h, s_tok, B, t.D, t.ldh, tid);
   __syncthreads();
@@ -292,7 +292,7 @@ __global__ __launch_bounds__(256) void logprob_argmax_tail_kernel(
     const int t = s_tok[tid];
     tok[tid] = t;
     vlm_window_advance(ctx, pos, B, tid, wn);
-    if (out_ring) out_ring[(size_t)(st % ring_len) * B + tid] = t;
+    if (out_ring) vlm_ring_store(out_ring, (size_t)(st % ring_len) * B + tid, t, wn);
   }
   // next step's input embeddings
   gather_rows_256(embed, h, s_tok, B, D, ldh, tid);

@@ -199,17 +199,28 @@ class _TokenPipe:
     def __init__(self, B: int, cap: int):
         self.buf = torch.empty(cap, B, dtype=torch.int32).pin_memory()
         self.events: List[Optional[torch.cuda.Event]] = [None] * cap
+        self.rows: List[Optional[torch.Tensor]] = [None] * cap
         self.cap = cap
 
     def push(self, idx: int, src: torch.Tensor):
         self.buf[idx % self.cap].copy_(src, non_blocking=True)
+        self.rows[idx % self.cap] = self.buf[idx % self.cap]
+        self._record(idx)
+
+    def push_host(self, idx: int, row: torch.Tensor):
+        """the step just enqueued writes its tokens into `row` itself (a slot of a pinned ring, _lib.DECODE_HOST_RING):
+        the event alone - no copy kernel between two replays"""
+        self.rows[idx % self.cap] = row
+        self._record(idx)
+
+    def _record(self, idx: int):
         ev = torch.cuda.Event()
         ev.record()
         self.events[idx % self.cap] = ev
 
     def get(self, idx: int) -> np.ndarray:
         self.events[idx % self.cap].synchronize()
-        return self.buf[idx % self.cap].numpy().copy()
+        return self.rows[idx % self.cap].numpy().copy()
 
 
 def _resolve_sampler(sampler, temperature, top_p, min_p, top_k, seed, **more):
@@ -292,6 +303,9 @@ def generate_step(input_ids, model, pixel_values, mask, *, max_tokens: int = DEF
     # per layer when the caller brings no prompt_cache.  Here: a bound on the paged sequence; its decode steps run captured over
     # the device-resident window (LanguageModel.decode_begin), eagerly only for what cannot live in a captured step
     max_kv_size = kwargs.pop("max_kv_size", None)
+    # tokens reach the host through the step's own store into a pinned ring (True) or a copy of st.tok behind every replay
+    # (False); None: the model's tuning (LanguageModel.TUNING_DEFAULTS["host_ring"], VLM_DECODE_HOST_RING for A/B runs)
+    host_ring = kwargs.pop("host_ring", None)
     # uniform quantized KV cache (reference ar.py:174-181,249-260,362: maybe_quantize_kv_cache after EVERY forward): from the
     # first forward that leaves the cache at quantized_kv_start tokens or more, the cache is a QuantizedKVCache
     kv_bits = kwargs.pop("kv_bits", None)
@@ -440,7 +454,9 @@ def generate_step(input_ids, model, pixel_values, mask, *, max_tokens: int = DEF
     seq = prompt_cache[0]._seq
     base_offset = seq.offset
 
-    lookahead = max(1, min(int(lookahead), st.ring_len - 1))
+    lookahead = max(1, min(int(lookahead), st.ring_len - 1))     # (< ring_len: no slot is rewritten before it was read)
+    if host_ring is None:
+        host_ring = bool(getattr(lm, "tuning", {}).get("host_ring"))
     win0 = seq.window_state() if st.window is not None else None
     if st.window is not None and not own_cache:
         # steps enqueued ahead of the consumer overwrite the oldest entries of a window (an unbounded cache only writes slots the
@@ -467,9 +483,12 @@ def generate_step(input_ids, model, pixel_values, mask, *, max_tokens: int = DEF
                                                    # at it (a stop token) has not advanced the matcher past the end
                     stage_mask(int(pipe.get(issued)[0]))
                 maybe_quantize_kv_cache()          # (the forward just enqueued may have carried the cache past the start)
-                lm.decode_run(st, 1, sargs, use_graph=use_graph, penalties=penalties)
+                lm.decode_run(st, 1, sargs, use_graph=use_graph, penalties=penalties, host_ring=host_ring)
                 issued += 1
-                pipe.push(issued, st.tok)
+                if host_ring:      # the sampling step counter stands at `issued` when this step runs (token 0 used step 0)
+                    pipe.push_host(issued, st.host_ring[issued % st.ring_len])
+                else:
+                    pipe.push(issued, st.tok)
                 if return_logprobs:
                     lps[issued % (lookahead + 2)] = st.logprobs[0].clone()
             tok = int(pipe.get(n)[0])

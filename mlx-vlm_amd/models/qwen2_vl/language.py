@@ -65,6 +65,7 @@ class DecodeState:
         self.act = A((max(B, 16), t.intermediate_size), bf)
         self.part_ml = A((B, Hq, nsplit, 2), torch.float32)
         self.out_ring = A((ring_len, B), i32, zero=True)
+        self.host_ring = None       # pinned twin of out_ring, allocated when a step first runs with _lib.DECODE_HOST_RING
         # rows at pitch VL = vocab rounded up to 8 (the engine's pitch: 16-byte aligned rows for any vocabulary, e.g. 32003)
         VL = (t.vocab_size + 7) & ~7
         self.logits = torch.empty(B, VL, dtype=bf, device=dev)[:, : t.vocab_size]
@@ -180,10 +181,15 @@ class DecodeState:
         """B < self.B: the step runs over the first B rows (every buffer is row-major, a prefix is a valid state).
         flags: _lib.DECODE_FUSED_TAIL = the step starts from h == embed[tok] and leaves the next step's h behind."""
         p = lambda t: t.data_ptr()  # noqa: E731
+        ring = self.out_ring
+        if int(flags) & _lib.DECODE_HOST_RING:
+            if self.host_ring is None:
+                self.host_ring = torch.zeros(self.ring_len, self.B, dtype=torch.int32).pin_memory()
+            ring = self.host_ring
         return _lib.DecodeArgs(self.B if B is None else int(B), p(self.tok), p(self.pos), p(self.ctx), p(self.step), p(self.h), p(self.qkv),
                                p(self.attn), p(self.act), p(self.logits),
                                p(self.logprobs) if (with_logprobs or temperature > 0) else None, p(self.scratch),
-                               p(self.part_o), p(self.part_ml), p(self.sample_ws), p(self.out_ring), self.ring_len,
+                               p(self.part_o), p(self.part_ml), p(self.sample_ws), p(ring), self.ring_len,
                                self.nsplit, float(temperature), float(top_p), float(min_p), int(top_k),
                                int(seed) & 0xFFFFFFFF, int(flags) | _lib.DECODE_ACT16,       # (self.act holds 16 rows)
                                C.pointer(pa) if (pa := self.penalty_args(penalties)) is not None else None)
@@ -352,8 +358,10 @@ class LanguageModel:
         self._init_pool()
 
     # decode-step tuning (results are identical under every setting up to bf16 ties; defaults from the measurements in
-    # DESIGN.md, environment overrides VLM_DECODE_<NAME> for A/B runs)
-    TUNING_DEFAULTS = {"fused_tail": 1, "mfma_gemv": 1, "attn_pagesplit": 16, "gemv_variant": 1, "attn_merge": 1}
+    # DESIGN.md, environment overrides VLM_DECODE_<NAME> for A/B runs).  gemv_variant 13 = bits 0, 2, 3 of VLM_TUNE_GEMV_VARIANT:
+    # down projection at 6 rows per workgroup, gate/up and head at 2 rows per wave (profiles/decode_slack_ab.txt); host_ring
+    # (tokens through a pinned ring, no copy kernel per step) measured +0.3-0.4 %, under the project's bar: off
+    TUNING_DEFAULTS = {"fused_tail": 1, "mfma_gemv": 1, "attn_pagesplit": 16, "gemv_variant": 13, "attn_merge": 1, "host_ring": 0}
 
     def apply_tuning(self, **over):
         L = _lib.lib()
@@ -935,9 +943,12 @@ class LanguageModel:
         q = (pool.kpool8.data_ptr(), pool.vpool8.data_ptr(), pool.ksb.data_ptr(), pool.vsb.data_ptr()) if q8 else (None,) * 4
         return _lib.KvPool(pool.kpool.data_ptr(), pool.vpool.data_ptr(), pool.layer_stride, bt.data_ptr(), pool.max_pages, *q)
 
-    def decode_run(self, st: DecodeState, n_steps: int, sampler_args: dict, use_graph: bool = True, penalties=None):
+    def decode_run(self, st: DecodeState, n_steps: int, sampler_args: dict, use_graph: bool = True, penalties=None,
+                   host_ring: bool = False):
         """Enqueue n_steps decode steps (graph replays when use_graph).  penalties: sample_utils.LogitsProcessors, or "rows":
-        the state's per-row tables (row_penalty_tables - what a token bitmask travels in)."""
+        the state's per-row tables (row_penalty_tables - what a token bitmask travels in).  host_ring: the steps write their
+        tokens into st.host_ring (pinned; slot = sampling step % ring_len) instead of st.out_ring - the caller reads them
+        there behind an event and enqueues no copy of st.tok."""
         L = _lib.lib()
         if st.window is None and any(s.rotating for s in st.seqs):
             raise NotImplementedError("max_kv_size: the captured step writes at slot = tokens seen; a rotating window runs "
@@ -953,12 +964,13 @@ class LanguageModel:
         # the fused tails (greedy: vlm_sample_greedy_advance; with a temperature: the sampler's last launch also advances and
         # gathers) read bf16 embedding rows
         fused = bool(self.tuning.get("fused_tail")) and not hasattr(self._w["embed"], "wq")
-        flags = (_lib.DECODE_FUSED_TAIL if fused else 0) | (_lib.DECODE_WINDOW if st.window is not None else 0)
+        flags = ((_lib.DECODE_FUSED_TAIL if fused else 0) | (_lib.DECODE_WINDOW if st.window is not None else 0) |
+                 (_lib.DECODE_HOST_RING if host_ring else 0))
         args = st.args(flags=flags, penalties=penalties, **sampler_args)
         if os.environ.get("VLM_NO_GRAPH"):           # diagnostics: every launch of the step visible to the HIP runtime's log
             use_graph = False
         if use_graph:
-            key = (st.seq_row0, st.nsplit, fused, q8, st.window,
+            key = (st.seq_row0, st.nsplit, fused, bool(host_ring), q8, st.window,
                    penalties if isinstance(penalties, str) else penalties.key() if penalties else None,
                    tuple(sorted(sampler_args.items())))
             if st.graph_key != key or getattr(self, "_graph_owner", None) is not st:
