@@ -27,8 +27,27 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # GEMM loses its 5472 accumulator moves.  Results are bit-identical (profiles/r02_attn_prefill_probe.txt).
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function",
          "-Wno-unused-variable", "-Wno-pass-failed", "-mllvm", "-amdgpu-mfma-vgpr-form"]
+# -amdgpu-kernarg-preload-count: the command processor delivers the first 14 kernel-argument dwords in user SGPRs at wave
+# start, so a kernel's first loads do not wait for a cold scalar load of its own arguments.  The kernels of the one-row decode
+# step (143 dependent launches per token) order their parameters for it: everything the first loads and the weight stream
+# address with comes first (csrc/gemv_bf16.hip, csrc/attn_decode.hip; scripts/kernarg_entry_report.py shows what is left
+# ahead of them).  Every kernel keeps the scalar loads as a compatibility prologue for firmware that does not preload.
+# Only the translation units of that step get the flag: their kernels' entry code is what the report and the A/B cover, and
+# every other kernel (prefill GEMMs, attention, the batched decode forms) keeps the entry code it was measured with.
+# VLM_NO_KERNARG_PRELOAD=1 builds the same sources without it (A/B libraries, picked at run time with VLM_HIP_LIB).
+# (-> lib/libvlm_hip_nopreload.so).  Results are bit-identical; measurement: profiles/kernarg_preload.txt.
+PRELOAD_UNITS = ("gemv_bf16.hip", "attn_decode.hip", "sample.hip")
+PRELOAD_FLAGS = ["-mllvm", "-amdgpu-kernarg-preload-count=16"]
+if os.environ.get("VLM_NO_KERNARG_PRELOAD", "0") not in ("", "0"):      # objects and library of their own, next to the default
+    PRELOAD_FLAGS = []
+    OBJDIR = os.path.join(HERE, "build_nopreload")
+    LIB = os.path.join(LIBDIR, "libvlm_hip_nopreload.so")
 # measurement builds only (e.g. VLM_BUILD_DEFINES="VLM_GEMM_ABLATION GEMM_STAMPS"): never set for the shipped library
 FLAGS += ["-D" + d for d in os.environ.get("VLM_BUILD_DEFINES", "").split()]
+
+
+def flags_for(src: str):
+    return FLAGS + (PRELOAD_FLAGS if os.path.basename(src) in PRELOAD_UNITS else [])
 
 
 def sources():
@@ -47,7 +66,7 @@ def _compile(src: str, force: bool) -> str:
     newest = max([os.path.getmtime(src), _deps_mtime()] + [os.path.getmtime(i) for i in inc if os.path.exists(i)])
     if not force and os.path.exists(obj) and os.path.getmtime(obj) >= newest:
         return obj
-    cmd = [HIPCC, *FLAGS, "-c", src, "-o", obj]
+    cmd = [HIPCC, *flags_for(src), "-c", src, "-o", obj]
     r = subprocess.run(cmd, capture_output=True, text=True)
     if r.returncode != 0:
         raise RuntimeError(f"hipcc failed for {src}:\n{r.stdout}\n{r.stderr}")

@@ -354,19 +354,27 @@ __device__ __forceinline__ void pagesplit_finish(f32x4_t (&ot)[8], float m_run, 
 template <int G, bool IDENT, bool MERGE>
 __global__ __launch_bounds__(64) void attn_decode_pagesplit_kernel(
     const bf16_t* __restrict__ q, const bf16_t* __restrict__ kpool, const bf16_t* __restrict__ vpool,
-    const int* __restrict__ block_table, const int* __restrict__ kv_len, int ldq, int max_pages, int Hkv, int kv_len_add,
-    float scale_log2, int S, int ldo, float* part_o, float* part_ml, unsigned* tickets, bf16_t* __restrict__ out,
-    int unused_) {
+    const int* __restrict__ block_table, const int* __restrict__ kv_len, int ldq, int max_pages, int Hkv, int S,
+    int kv_len_add, float scale_log2, int ldo, int pad_, float* part_o, float* part_ml, unsigned* tickets,
+    bf16_t* __restrict__ out) {
   const int bh = blockIdx.x, b = bh / Hkv, g = bh % Hkv, s = blockIdx.y;
   const int lane = threadIdx.x, head = lane & 15, gq = lane >> 4;
-  // every kernel argument in ONE scalar-load batch at entry (the tail's arguments would otherwise be fetched lazily,
-  // one more round trip on the path to the ticket)
-  asm volatile("" ::"s"(part_o), "s"(part_ml), "s"(tickets), "s"(out), "s"(S), "s"(ldo));
+  // The first 14 argument dwords (q .. S) are everything the address of a table / length / Q / K / V load depends on, the
+  // stride S of the page walk included: preloaded into SGPRs (build.py, -amdgpu-kernarg-preload-count) they cost no
+  // scalar-load round trip.  The rest (kv_len_add and the softmax scale, first used on loaded data, and the tail's arguments)
+  // is pulled in ONE scalar-load batch by the empty asm below, which the walk runs right behind the issue of a page's loads:
+  // at entry it put a full lgkmcnt(0) in front of them, and without it the tail's arguments are fetched lazily, one more
+  // round trip on the path to the ticket.
+  const auto args_batch = [&] {
+    // (pad_ fills the hole in front of the pointers and is "used" too: a dead dword in the middle of the batch gets its
+    //  register reused at once, and the write to it waits for the whole batch - ahead of the K / V loads again)
+    asm volatile("" ::"s"(part_o), "s"(part_ml), "s"(tickets), "s"(out), "s"(kv_len_add), "s"(scale_log2), "s"(ldo), "s"(pad_));
+  };
   f32x4_t ot[8];
   float m_run, l_run;
   int npages;
   vlm_pagesplit_walk<G, IDENT>(q, kpool, vpool, block_table, kv_len, ldq, max_pages, Hkv, kv_len_add, scale_log2, S, b, g, s, lane, ot,
-                               m_run, l_run, npages);
+                               m_run, l_run, npages, args_batch);
 
   pagesplit_finish<G, MERGE>(ot, m_run, l_run, npages, bh, b, g, s, S, Hkv, lane, ldo, part_o, part_ml, tickets, out);
 }
@@ -742,7 +750,7 @@ extern "C" int vlm_attn_decode_paged_split(const void* q, int ldq, const void* k
 #define GO1(GV, ID, MG)                                                                                                  \
   hipLaunchKernelGGL((attn_decode_pagesplit_kernel<GV, ID, MG>), grid, dim3(64), 0, st, (const bf16_t*)q,                 \
                      (const bf16_t*)kpool, (const bf16_t*)vpool, (const int*)block_table, (const int*)kv_len, ldq, max_pages, \
-                     Hkv, kv_len_add, sl2, nsplit, ldo, (float*)part_o, (float*)part_ml, (unsigned*)tickets, (bf16_t*)out, 0)
+                     Hkv, nsplit, kv_len_add, sl2, ldo, 0, (float*)part_o, (float*)part_ml, (unsigned*)tickets, (bf16_t*)out)
 #define GO(GV)                                                                                                           \
   do {                                                                                                                   \
     if (!block_table) { if (out) GO1(GV, true, true); else GO1(GV, true, false); }                                       \

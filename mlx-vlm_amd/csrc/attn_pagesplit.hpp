@@ -31,12 +31,15 @@ __device__ __forceinline__ void vlm_pack_p_hilo(const f32x4_t (&st)[4], bf16x8_t
   }
 }
 
-template <int G, bool IDENT>
+// issued(): run once per page right behind the issue of the page's K / V loads - the caller's hook for what must not come
+// in front of them (attn_decode.hip: the scalar-load batch of the kernel arguments that are not preloaded)
+struct VlmNoHook { __device__ __forceinline__ void operator()() const {} };
+template <int G, bool IDENT, class Issued = VlmNoHook>
 __device__ __forceinline__ void vlm_pagesplit_walk(const bf16_t* __restrict__ q, const bf16_t* __restrict__ kpool,
                                                    const bf16_t* __restrict__ vpool, const int* __restrict__ block_table,
                                                    const int* __restrict__ kv_len, int ldq, int max_pages, int Hkv, int kv_len_add,
                                                    float scale_log2, int S, int b, int g, int s, int lane, f32x4_t (&ot)[8],
-                                                   float& m_run, float& l_run, int& npages) {
+                                                   float& m_run, float& l_run, int& npages, Issued issued = Issued()) {
   constexpr int HD = VLM_HD, PAGE = VLM_PAGE;
   const int head = lane & 15, gq = lane >> 4;
   int pi = s;
@@ -72,6 +75,8 @@ __device__ __forceinline__ void vlm_pagesplit_walk(const bf16_t* __restrict__ q,
 #pragma unroll
       for (int u = 0; u < 2; ++u)
         vf[dt][u] = *reinterpret_cast<const u32x4_t*>(vp + (size_t)(16 * dt) * PAGE + 32 * u);
+    __builtin_amdgcn_sched_barrier(0);
+    issued();
     const int pc = pi;     // the page being processed
     pi += S;
     const size_t next_page = IDENT ? (size_t)b * max_pages + min(pi, max_pages - 1) : (size_t)trow[min(pi, max_pages - 1)];

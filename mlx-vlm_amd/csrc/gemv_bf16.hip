@@ -78,38 +78,35 @@ __device__ __forceinline__ float dot8(const u32x4_t w, const u32x4_t x, float ac
 // ------------------------------------------------------------------------------------------
 // row-wave kernel: K <= 512 * KC
 // ------------------------------------------------------------------------------------------
+// Parameter order: gfx950 delivers the first 14 kernel-argument dwords in SGPRs at wave start (build.py,
+// -amdgpu-kernarg-preload-count), so they hold everything an address of the loads issued up to and including the weight
+// stream depends on; what is used later (y, ldy, ldres, eps, the by-value structs) follows and arrives by a scalar load
+// that is waited for at its first use.  Five pointers and four ints fill the 14 dwords, so three slots change meaning with
+// the prologue (the launcher fills them, unpacked below):
+//   xsrc   x [M][ldx] bf16                      | PRO_ATTN_PS: the attention's partial O, fp32 (AttnProArgs::part_o)
+//   xaux   norm_w [K] bf16 (norm prologues)     | PRO_ATTN_PS: its (m, l) pairs (AttnProArgs::part_ml)
+//   ldx    leading dimension of x               | PRO_ATTN_PS: S | D << 8 (x has no leading dimension: it is the merge)
+// PRO_ATTN (the general merge) keeps reading AttnProArgs.  The qkv form (EPI_ROPE_KV) needs 22 dwords ahead of its weight
+// stream - these plus pos, slot, inv_freq, (Hq, Hkv, D) and long_from of RopeKvArgs: its x / norm_w loads go out on the
+// preloaded arguments and the rest waits for the scalar load behind them (profiles/kernarg_preload.txt).
 template <int R, int KC, int MB, int PRO, int EPI>
-__global__ __launch_bounds__(256) void gemv_rowwave_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ W,
-                                                           const bf16_t* __restrict__ bias, const bf16_t* __restrict__ res,
-                                                           const bf16_t* __restrict__ norm_w, bf16_t* __restrict__ y, int N,
-                                                           int K, int ldx, int ldw, int ldy, int ldres, float eps,
+__global__ __launch_bounds__(256) void gemv_rowwave_kernel(const bf16_t* __restrict__ W, const void* __restrict__ xsrc,
+                                                           const void* __restrict__ xaux, const bf16_t* __restrict__ bias,
+                                                           const bf16_t* __restrict__ res, int N, int K, int ldw, int ldx,
+                                                           bf16_t* __restrict__ y, int ldy, int ldres, float eps,
                                                            RopeKvArgs rk, AttnProArgs ap) {
+  const bf16_t* __restrict__ x = static_cast<const bf16_t*>(xsrc);
+  const bf16_t* __restrict__ norm_w = static_cast<const bf16_t*>(xaux);
+  if (PRO == PRO_ATTN_PS) {
+    ap.part_o = static_cast<const float*>(xsrc);
+    ap.part_ml = static_cast<const float*>(xaux);
+    ap.S = ldx & 255;
+    ap.D = ldx >> 8;
+  }
   extern __shared__ __attribute__((aligned(16))) char smem[];   // xs[MB][K] bf16
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int nchunk = K >> 3;
   const int gw = blockIdx.x * 4 + wave;
-
-  // ---- which rows does this wave own?
-  int row[R];
-  bool rope_pair = false;
-  int rope_head = 0, rope_j = 0;
-  if (EPI == EPI_ROPE_KV) {
-    const int half = rk.D >> 1, n_pair = (rk.Hq + rk.Hkv) * half;
-    if (gw < n_pair) {
-      rope_pair = true;
-      rope_head = gw / half;
-      rope_j = gw % half;
-      row[0] = rope_head * rk.D + rope_j;
-      row[R - 1] = row[0] + half;
-    } else {
-      row[0] = (rk.Hq + rk.Hkv) * rk.D + 2 * (gw - n_pair);
-      row[R - 1] = row[0] + 1;
-    }
-  } else {
-#pragma unroll
-    for (int r = 0; r < R; ++r) row[r] = gw * R + r;
-  }
-  const bool active = row[0] < N;
 
   // ---- loads are returned in issue order (vmcnt), so the SMALL latency-critical ones go first: the
   //      activation row for the norm prologue and the epilogue operands; then every weight load of the
@@ -143,6 +140,30 @@ __global__ __launch_bounds__(256) void gemv_rowwave_kernel(const bf16_t* __restr
       if (MB > 4) xv2[c] = *reinterpret_cast<const u32x4_t*>(x + (size_t)(4 + wave) * ldx + (size_t)chc * 8);
     }
   }
+  // ---- which rows does this wave own?  (Behind the norm prologue's loads: in the qkv form the answer needs RopeKvArgs,
+  //      which is not among the preloaded arguments - the x / norm_w loads above go out while its scalar load is in flight)
+  if (EPI == EPI_ROPE_KV) __builtin_amdgcn_sched_barrier(0);
+  int row[R];
+  bool rope_pair = false;
+  int rope_head = 0, rope_j = 0;
+  if (EPI == EPI_ROPE_KV) {
+    const int half = rk.D >> 1, n_pair = (rk.Hq + rk.Hkv) * half;
+    if (gw < n_pair) {
+      rope_pair = true;
+      rope_head = gw / half;
+      rope_j = gw % half;
+      row[0] = rope_head * rk.D + rope_j;
+      row[R - 1] = row[0] + half;
+    } else {
+      row[0] = (rk.Hq + rk.Hkv) * rk.D + 2 * (gw - n_pair);
+      row[R - 1] = row[0] + 1;
+    }
+  } else {
+#pragma unroll
+    for (int r = 0; r < R; ++r) row[r] = gw * R + r;
+  }
+  const bool active = row[0] < N;
+
   // PRO_ATTN fast path (<= 4 splits, MB <= 2): the split merge is one 8-element chunk of x per thread; its loads
   // (m/l pairs + the partial O rows) are independent of everything, so they go out here, ahead of the weight stream
   // - the merge then costs no extra memory round trip (the first version merged through LDS in three dependent
@@ -516,9 +537,13 @@ template <int R, int KC, int MB, int PRO, int EPI>
 int launch_rw(const Args& a, int n_waves) {
   const int grid = vlm_cdiv(n_waves, 4);
   const size_t lds = (size_t)MB * a.K * 2 + (PRO == PRO_ATTN ? (size_t)MB * a.ap.Hq * a.ap.S * 2 * sizeof(float) : 0);
-  hipLaunchKernelGGL((gemv_rowwave_kernel<R, KC, MB, PRO, EPI>), dim3(grid), dim3(256), lds, a.st, (const bf16_t*)a.x,
-                     (const bf16_t*)a.W, (const bf16_t*)a.bias, (const bf16_t*)a.res, (const bf16_t*)a.norm_w,
-                     (bf16_t*)a.y, a.N, a.K, a.ldx, a.ldw, a.ldy, a.ldres, a.eps, a.rk, a.ap);
+  // the two slots that change meaning with the prologue (see the kernel's parameter list)
+  const void* xsrc = PRO == PRO_ATTN_PS ? (const void*)a.ap.part_o : a.x;
+  const void* xaux = PRO == PRO_ATTN_PS ? (const void*)a.ap.part_ml : a.norm_w;
+  const int ldx = PRO == PRO_ATTN_PS ? (a.ap.S | a.ap.D << 8) : a.ldx;
+  hipLaunchKernelGGL((gemv_rowwave_kernel<R, KC, MB, PRO, EPI>), dim3(grid), dim3(256), lds, a.st, (const bf16_t*)a.W, xsrc,
+                     xaux, (const bf16_t*)a.bias, (const bf16_t*)a.res, a.N, a.K, a.ldw, ldx, (bf16_t*)a.y, a.ldy, a.ldres,
+                     a.eps, a.rk, a.ap);
   return launch_err();
 }
 
