@@ -591,10 +591,20 @@ int vlm_llm_decode_launches(void* handle);
                                        Hq * D <= 1536) with 4 rows per wave - half as many workgroups repeat the merge;
                                        bit 5 (32): RMSNorm-prologue GEMVs of ONE row: the three waves of a workgroup that do not
                                        store the normalised row fetch x / norm_w through a zero-extent buffer resource, i.e.
-                                       generate no memory traffic for them.
-                                       A row's sum does not depend on the rows its wave owns: every bit gives the same bytes.
-                                       Measured (profiles/decode_slack_ab.txt): bits 0, 2, 3 win - the Python layer sets 13 -
-                                       bit 4 loses 1.7 %, bit 5 changes nothing) */
+                                       generate no memory traffic for them;
+                                       bits 8, 9 (256, 512): the knob's launches of the same step that are no GEMV - the
+                                       partial-only page-split attention (vlm_attn_decode_paged_split with out == NULL, at most
+                                       64 (row, kv head) pairs) splits the eight 16-row output tiles of a page over 2 (bit 8) or
+                                       4 (bit 9; wins over bit 8) workgroups in grid z: each computes the scores and softmax
+                                       statistics of its pages as the single workgroup does and loads V, multiplies and stores
+                                       for its own tiles only; z = 0 stores (m, l).
+                                       A row's sum does not depend on the rows its wave owns, and an output tile not on the
+                                       workgroup that owns it: every bit gives the same bytes.
+                                       Measured (profiles/decode_slack_ab.txt, profiles/latency_launches_ab.txt): bits 0, 2, 3,
+                                       9 win - the Python layer sets 525 - bit 4 loses 1.7 %, bit 5 changes nothing, bit 8
+                                       gains half of bit 9; bits 6 and 7 are unused: a qkv form with no scalar-load wait ahead
+                                       of its weights (+0.6 %, under the bar) and the o_proj in three-wave workgroups (-0.7 %)
+                                       were measured on them and left the library) */
 #define VLM_TUNE_ATTN_MERGE 9       /* where the page-split attention of a ONE-row step is merged: 1 (default) = in the o_proj
                                        GEMV's prologue (partial-only attention launch, vlm_gemv_attn_out_bf16; needs bf16 Wo,
                                        Hq * D <= 2048, <= 16 splits), 0 = by the attention launch's last-arriving workgroup */

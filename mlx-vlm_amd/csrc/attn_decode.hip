@@ -379,6 +379,35 @@ __global__ __launch_bounds__(64) void attn_decode_pagesplit_kernel(
   pagesplit_finish<G, MERGE>(ot, m_run, l_run, npages, bh, b, g, s, S, Hkv, lane, ldo, part_o, part_ml, tickets, out);
 }
 
+// The partial-only launch with the output dimensions of a page split over DZ workgroups (grid z): every z computes the scores
+// and the softmax statistics of its pages exactly as above, and keeps 8 / DZ of the eight 16-row output tiles - their V rows,
+// their PV MFMAs, their stores.  z = 0 alone stores (m, l).  Same layout [b][head][s][d], same bytes; K is read DZ times.
+template <int G, bool IDENT, int DZ>
+__global__ __launch_bounds__(64) void attn_decode_pagesplit_dz_kernel(
+    const bf16_t* __restrict__ q, const bf16_t* __restrict__ kpool, const bf16_t* __restrict__ vpool,
+    const int* __restrict__ block_table, const int* __restrict__ kv_len, int ldq, int max_pages, int Hkv, int S,
+    int kv_len_add, float scale_log2, float* part_o, float* part_ml) {
+  const int bh = blockIdx.x, b = bh / Hkv, g = bh % Hkv, s = blockIdx.y, z = blockIdx.z;
+  const int lane = threadIdx.x, head = lane & 15, gq = lane >> 4;
+  const auto args_batch = [&] { asm volatile("" ::"s"(part_o), "s"(part_ml), "s"(kv_len_add), "s"(scale_log2)); };   // (as above)
+  constexpr int NDT = 8 / DZ;
+  f32x4_t ot[NDT];
+  float m_run, l_run;
+  int npages;
+  vlm_pagesplit_walk<G, IDENT, decltype(args_batch), DZ>(q, kpool, vpool, block_table, kv_len, ldq, max_pages, Hkv, kv_len_add,
+                                                         scale_log2, S, b, g, s, lane, ot, m_run, l_run, npages, args_batch, z);
+  l_run = col4_sum(l_run);
+  if (head < G) {
+    const size_t e = ((size_t)b * (Hkv * G) + (g * G + head)) * S + s;
+    if (gq == 0 && z == 0) *reinterpret_cast<float2*>(part_ml + e * 2) = make_float2(m_run, l_run);
+    if (m_run != -INFINITY) {
+      float* po = part_o + e * HD + 4 * gq + 16 * NDT * z;
+#pragma unroll
+      for (int dt = 0; dt < NDT; ++dt) *reinterpret_cast<f32x4_t*>(po + 16 * dt) = ot[dt];
+    }
+  }
+}
+
 // ------------------------------------------------------------------------------------------------------------------
 // Uniform 8-bit KV cache (reference QuantizedKVCache, mlx_vlm/models/cache.py:233-334; its attention
 // quantized_scaled_dot_product_attention, models/base.py:260-302; the switch-over maybe_quantize_kv_cache,
@@ -734,6 +763,9 @@ extern "C" int vlm_attn_decode_paged(const void* q, int ldq, const void* kpool, 
   return VLM_OK;
 }
 
+namespace { int g_attn_dsplit = 1; }   // 1, 2 or 4 workgroups per page over the output dimensions (bits 8, 9 of VLM_TUNE_GEMV_VARIANT)
+VLM_INTERNAL void vlm_attn_set_dsplit(int dz) { g_attn_dsplit = dz == 2 || dz == 4 ? dz : 1; }
+
 extern "C" int vlm_attn_decode_paged_split(const void* q, int ldq, const void* kpool, const void* vpool,
                                            const void* block_table, int max_pages, const void* kv_len, int kv_len_add, int B,
                                            int Hq, int Hkv, int D, float scale, int nsplit, void* part_o, void* part_ml,
@@ -746,6 +778,35 @@ extern "C" int vlm_attn_decode_paged_split(const void* q, int ldq, const void* k
   const int G = Hq / Hkv;
   hipStream_t st = (hipStream_t)stream;
   const float sl2 = scale * 1.44269504088896340736f;
+  // one-row steps (at most 64 (row, kv head) pairs) that leave the merge to the o_proj: the output tiles over grid z
+  const int dz = (!out && B * Hkv <= 64) ? g_attn_dsplit : 1;
+  if (dz > 1) {
+    dim3 gridz(B * Hkv, nsplit, dz);
+#define GOZ1(GV, ID, DZV)                                                                                                \
+  hipLaunchKernelGGL((attn_decode_pagesplit_dz_kernel<GV, ID, DZV>), gridz, dim3(64), 0, st, (const bf16_t*)q,            \
+                     (const bf16_t*)kpool, (const bf16_t*)vpool, (const int*)block_table, (const int*)kv_len, ldq, max_pages, \
+                     Hkv, nsplit, kv_len_add, sl2, (float*)part_o, (float*)part_ml)
+#define GOZ(GV)                                                                                                          \
+  do {                                                                                                                   \
+    if (!block_table) { if (dz == 2) GOZ1(GV, true, 2); else GOZ1(GV, true, 4); }                                        \
+    else { if (dz == 2) GOZ1(GV, false, 2); else GOZ1(GV, false, 4); }                                                   \
+  } while (0)
+    switch (G) {
+      case 1: GOZ(1); break;
+      case 2: GOZ(2); break;
+      case 3: GOZ(3); break;
+      case 4: GOZ(4); break;
+      case 5: GOZ(5); break;
+      case 6: GOZ(6); break;
+      case 7: GOZ(7); break;
+      case 8: GOZ(8); break;
+      default: return VLM_ERR_SHAPE;
+    }
+#undef GOZ
+#undef GOZ1
+    VLM_CHECK_LAUNCH();
+    return VLM_OK;
+  }
   dim3 grid(B * Hkv, nsplit);
 #define GO1(GV, ID, MG)                                                                                                  \
   hipLaunchKernelGGL((attn_decode_pagesplit_kernel<GV, ID, MG>), grid, dim3(64), 0, st, (const bf16_t*)q,                 \

@@ -33,14 +33,19 @@ __device__ __forceinline__ void vlm_pack_p_hilo(const f32x4_t (&st)[4], bf16x8_t
 
 // issued(): run once per page right behind the issue of the page's K / V loads - the caller's hook for what must not come
 // in front of them (attn_decode.hip: the scalar-load batch of the kernel arguments that are not preloaded)
+// DZ > 1 (the partial-only launch of a one-row step, attn_decode.hip): the walk keeps only the 8 / DZ output tiles
+// dt = z * 8 / DZ + i - it loads their V rows, runs their PV MFMAs and leaves them in ot[i]; q, K, the scores and the
+// softmax statistics are those of DZ = 1, so m_run, l_run and every tile it keeps carry the same bits in every z.
 struct VlmNoHook { __device__ __forceinline__ void operator()() const {} };
-template <int G, bool IDENT, class Issued = VlmNoHook>
+template <int G, bool IDENT, class Issued = VlmNoHook, int DZ = 1>
 __device__ __forceinline__ void vlm_pagesplit_walk(const bf16_t* __restrict__ q, const bf16_t* __restrict__ kpool,
                                                    const bf16_t* __restrict__ vpool, const int* __restrict__ block_table,
                                                    const int* __restrict__ kv_len, int ldq, int max_pages, int Hkv, int kv_len_add,
-                                                   float scale_log2, int S, int b, int g, int s, int lane, f32x4_t (&ot)[8],
-                                                   float& m_run, float& l_run, int& npages, Issued issued = Issued()) {
-  constexpr int HD = VLM_HD, PAGE = VLM_PAGE;
+                                                   float scale_log2, int S, int b, int g, int s, int lane, f32x4_t (&ot)[8 / DZ],
+                                                   float& m_run, float& l_run, int& npages, Issued issued = Issued(), int z = 0) {
+  static_assert(DZ == 1 || DZ == 2 || DZ == 4, "output tiles per workgroup: 8, 4 or 2");
+  constexpr int HD = VLM_HD, PAGE = VLM_PAGE, NDT = 8 / DZ;
+  const int dt0 = DZ == 1 ? 0 : z * NDT;
   const int head = lane & 15, gq = lane >> 4;
   int pi = s;
   const int* trow = IDENT ? nullptr : block_table + (size_t)b * max_pages;
@@ -55,7 +60,7 @@ __device__ __forceinline__ void vlm_pagesplit_walk(const bf16_t* __restrict__ q,
   }
   __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-  for (int i = 0; i < 8; ++i) ot[i] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+  for (int i = 0; i < NDT; ++i) ot[i] = f32x4_t{0.f, 0.f, 0.f, 0.f};
   m_run = -INFINITY;
   l_run = 0.f;
   int len = 0;
@@ -64,17 +69,17 @@ __device__ __forceinline__ void vlm_pagesplit_walk(const bf16_t* __restrict__ q,
     if (!IDENT) asm volatile("s_waitcnt vmcnt(0)" : "+v"(len_raw), "+v"(page)::"memory");
     const bf16_t* kp = kpool + (page * Hkv + g) * (size_t)(HD / 8) * PAGE * 8 + ((size_t)gq * PAGE + head) * 8;
     const bf16_t* vp = vpool + (page * Hkv + g) * (size_t)HD * PAGE + (size_t)head * PAGE + 8 * gq;
-    u32x4_t kf[4][4], vf[8][2];
+    u32x4_t kf[4][4], vf[NDT][2];
 #pragma unroll
     for (int t = 0; t < 4; ++t)
 #pragma unroll
       for (int ds = 0; ds < 4; ++ds)
         kf[t][ds] = *reinterpret_cast<const u32x4_t*>(kp + ((size_t)(4 * ds) * PAGE + 16 * t) * 8);
 #pragma unroll
-    for (int dt = 0; dt < 8; ++dt)
+    for (int dt = 0; dt < NDT; ++dt)
 #pragma unroll
       for (int u = 0; u < 2; ++u)
-        vf[dt][u] = *reinterpret_cast<const u32x4_t*>(vp + (size_t)(16 * dt) * PAGE + 32 * u);
+        vf[dt][u] = *reinterpret_cast<const u32x4_t*>(vp + (size_t)(16 * (dt0 + dt)) * PAGE + 32 * u);
     __builtin_amdgcn_sched_barrier(0);
     issued();
     const int pc = pi;     // the page being processed
@@ -94,7 +99,10 @@ __device__ __forceinline__ void vlm_pagesplit_walk(const bf16_t* __restrict__ q,
         st[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, kf[t][ds]), qf[ds], st[t], 0, 0, 0);
     }
     if (IDENT) {
-      asm volatile("s_waitcnt vmcnt(16)" : "+v"(len_raw)::"memory");
+      // len, q and K have arrived once no more than the page's V loads (two per tile kept) are outstanding
+      if (DZ == 1) asm volatile("s_waitcnt vmcnt(16)" : "+v"(len_raw)::"memory");
+      if (DZ == 2) asm volatile("s_waitcnt vmcnt(8)" : "+v"(len_raw)::"memory");
+      if (DZ == 4) asm volatile("s_waitcnt vmcnt(4)" : "+v"(len_raw)::"memory");
       len = __builtin_amdgcn_readfirstlane(len_raw) + kv_len_add;
       npages = (len + PAGE - 1) / PAGE;
     }
@@ -126,7 +134,7 @@ __device__ __forceinline__ void vlm_pagesplit_walk(const bf16_t* __restrict__ q,
     bf16x8_t pb[2], pl[2];
     vlm_pack_p_hilo(st, pb, pl);
 #pragma unroll
-    for (int dt = 0; dt < 8; ++dt) {
+    for (int dt = 0; dt < NDT; ++dt) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) ot[dt][r] *= alpha;
 #pragma unroll

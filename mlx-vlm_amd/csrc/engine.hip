@@ -170,7 +170,10 @@ extern "C" int vlm_llm_set_tuning(void* handle, int key, int value) {
     case VLM_MODE_WINDOW_RING_POS: if (value < 0 || value > 1) return 1; slot = &m->tune.win_ring_pos; break;
     default: return 1;
   }
-  if (key == VLM_TUNE_GEMV_VARIANT) vlm_gemv_set_variant(value);
+  if (key == VLM_TUNE_GEMV_VARIANT) {
+    vlm_gemv_set_variant(value);
+    vlm_attn_set_dsplit((value & 512) ? 4 : (value & 256) ? 2 : 1);
+  }
   if (*slot == value) return 0;
   *slot = value;
   for (DecodeGraph& g : m->graphs) drop_graph(g);     // the captured steps bake the tuning in

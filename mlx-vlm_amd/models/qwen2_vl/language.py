@@ -358,10 +358,12 @@ class LanguageModel:
         self._init_pool()
 
     # decode-step tuning (results are identical under every setting up to bf16 ties; defaults from the measurements in
-    # DESIGN.md, environment overrides VLM_DECODE_<NAME> for A/B runs).  gemv_variant 13 = bits 0, 2, 3 of VLM_TUNE_GEMV_VARIANT:
-    # down projection at 6 rows per workgroup, gate/up and head at 2 rows per wave (profiles/decode_slack_ab.txt); host_ring
-    # (tokens through a pinned ring, no copy kernel per step) measured +0.3-0.4 %, under the project's bar: off
-    TUNING_DEFAULTS = {"fused_tail": 1, "mfma_gemv": 1, "attn_pagesplit": 16, "gemv_variant": 13, "attn_merge": 1, "host_ring": 0}
+    # DESIGN.md, environment overrides VLM_DECODE_<NAME> for A/B runs).  gemv_variant 525 = bits 0, 2, 3, 9 of
+    # VLM_TUNE_GEMV_VARIANT: down projection at 6 rows per workgroup, gate/up and head at 2 rows per wave
+    # (profiles/decode_slack_ab.txt), the partial-only attention of a one-row step over 4 workgroups per page
+    # (profiles/latency_launches_ab.txt); host_ring (tokens through a pinned ring, no copy kernel per step) measured
+    # +0.2-0.4 % in four series, under the project's bar each time: off
+    TUNING_DEFAULTS = {"fused_tail": 1, "mfma_gemv": 1, "attn_pagesplit": 16, "gemv_variant": 525, "attn_merge": 1, "host_ring": 0}
 
     def apply_tuning(self, **over):
         L = _lib.lib()
