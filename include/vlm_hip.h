@@ -555,6 +555,13 @@ typedef struct vlm_decode_args {
                                    step % ring_len once the step has completed (an event behind it) and no device-to-host copy is
                                    enqueued between two steps.  The host must have read a slot before the step ring_len later is
                                    enqueued.  Same tokens; part of the graph key like every flag.  A bit added within ABI v8. */
+#define VLM_DECODE_SPLITS_SHIFT 4 /* bits 4, 5 (added within ABI v8): c = (flags >> 4) & 3.  c > 0: a ONE-row step whose page-split
+                                   attention is merged in the o_proj prologue (VLM_TUNE_ATTN_MERGE) runs both launches over
+                                   4 c splits instead of VLM_TUNE_ATTN_PAGESPLIT.  The caller promises ctx + 1 <= 256 c for
+                                   every replay: each split then owns at most one page, as under 16 splits, and the step gives
+                                   the same bytes (a longer context is still attended over in full - other bits).  Ignored by
+                                   every other step (more rows, 8-bit pools, a window, VLM_TUNE_ATTN_MERGE 0). */
+#define VLM_DECODE_SPLITS_MASK (3 << VLM_DECODE_SPLITS_SHIFT)
 
 int vlm_llm_create(const vlm_llm_config* cfg, void** handle);          /* (host) */
 int vlm_llm_destroy(void* handle);
@@ -598,13 +605,19 @@ int vlm_llm_decode_launches(void* handle);
                                        4 (bit 9; wins over bit 8) workgroups in grid z: each computes the scores and softmax
                                        statistics of its pages as the single workgroup does and loads V, multiplies and stores
                                        for its own tiles only; z = 0 stores (m, l).
-                                       A row's sum does not depend on the rows its wave owns, and an output tile not on the
-                                       workgroup that owns it: every bit gives the same bytes.
-                                       Measured (profiles/decode_slack_ab.txt, profiles/latency_launches_ab.txt): bits 0, 2, 3,
-                                       9 win - the Python layer sets 525 - bit 4 loses 1.7 %, bit 5 changes nothing, bit 8
-                                       gains half of bit 9; bits 6 and 7 are unused: a qkv form with no scalar-load wait ahead
-                                       of its weights (+0.6 %, under the bar) and the o_proj in three-wave workgroups (-0.7 %)
-                                       were measured on them and left the library) */
+                                       bit 11 (2048): vlm_gemv_attn_out_bf16 over at most 4 / 8 / 12 splits reads that many
+                                       (m, l, O) slots ahead of its weights, not all 16 (dead slots are dropped by a select either
+                                       way), and the Python layer asks for such launches: a one-row greedy step carries the
+                                       context class of VLM_DECODE_SPLITS_SHIFT in its flags.
+                                       A row's sum does not depend on the rows its wave owns, an output tile not on the
+                                       workgroup that owns it, a merge not on slots that hold no page: every bit gives the same
+                                       bytes.
+                                       Measured (profiles/decode_slack_ab.txt, profiles/latency_launches_ab.txt,
+                                       profiles/split_classes_ab.txt): bits 0, 2, 3, 9, 11 win - the Python layer sets 2573 - bit 4
+                                       loses 1.7 %, bit 5 changes nothing, bit 8 gains half of bit 9; bits 6, 7 and 10 are unused:
+                                       a qkv form with no scalar-load wait ahead of its weights (+0.6 %, under the bar), the o_proj
+                                       in three-wave workgroups (-0.7 %) and the greedy tail's log-sum-exp partials written by the
+                                       head GEMV (-0.5 %) were measured on them and left the library) */
 #define VLM_TUNE_ATTN_MERGE 9       /* where the page-split attention of a ONE-row step is merged: 1 (default) = in the o_proj
                                        GEMV's prologue (partial-only attention launch, vlm_gemv_attn_out_bf16; needs bf16 Wo,
                                        Hq * D <= 2048, <= 16 splits), 0 = by the attention launch's last-arriving workgroup */

@@ -426,6 +426,11 @@ static int decode_impl(Llm* m, const vlm_decode_args* a, void* stream, int* laun
     // ... and for ONE row over bf16 Wo the merge moves into the o_proj prologue: the attention launch ends at its partial
     // stores (no ticket, no last-arriver pass)
     const bool merge_in_oproj = psplit && tn.attn_merge && B == 1 && !w.wo_sb && Hq * hd <= 2048 && psplit <= 16;
+    // ... over as many splits as the caller's context class needs (VLM_DECODE_SPLITS_SHIFT: 4, 8 or 12; up to 256 tokens per 4
+    // splits every split owns at most one page, as under 16): the attention launches fewer workgroups, the o_proj prologue
+    // reads fewer dead (m, l, O) slots in front of its weights (gemv_bf16.hip PRO_ATTN_PS4 / 8 / 12), the bytes are the same
+    const int split_class = (a->flags & VLM_DECODE_SPLITS_MASK) >> VLM_DECODE_SPLITS_SHIFT;
+    if (split_class && merge_in_oproj && !q8 && !(a->flags & VLM_DECODE_WINDOW) && 4 * split_class < psplit) psplit = 4 * split_class;
     if (q8) {
       const size_t lo = (size_t)i * m->kv.layer_stride;                   // elements == bytes of the u8 pools
       TRY(vlm_attn_decode_paged_q8(a->qkv, QKV, kp, vp, off(m->kv.kpool8, lo), off(m->kv.vpool8, lo),

@@ -34,8 +34,15 @@ namespace {
 // PRO_RMSNORM_1W (MB == 1, variant bit 5): PRO_RMSNORM whose waves 1..3 - which normalise the row again and store nothing -
 // fetch x and norm_w through a buffer resource of ZERO extent: their loads are out of range, return zeros and reach no cache
 // (measured: the duplicate loads were free, no effect on the step - profiles/decode_slack_ab.txt; A/B only)
-enum { PRO_NONE = 0, PRO_RMSNORM = 1, PRO_ATTN = 2, PRO_ATTN_PS = 3, PRO_RMSNORM_1W = 4 };
+// PRO_ATTN_PS4 / 8 / 12: PRO_ATTN_PS reading 4 / 8 / 12 split slots instead of VLM_MERGE_S = 16 (a launch over S splits takes the
+// smallest form that holds them: the slots >= S are dropped by a select, so every form gives the bytes of PRO_ATTN_PS, and a
+// short context does not pay 40 B per thread and dead slot in front of the weight stream)
+enum { PRO_NONE = 0, PRO_RMSNORM = 1, PRO_ATTN = 2, PRO_ATTN_PS = 3, PRO_RMSNORM_1W = 4, PRO_ATTN_PS4 = 5, PRO_ATTN_PS8 = 6,
+       PRO_ATTN_PS12 = 7 };
 constexpr bool is_norm(int pro) { return pro == PRO_RMSNORM || pro == PRO_RMSNORM_1W; }
+constexpr bool is_ps(int pro) { return pro == PRO_ATTN_PS || pro == PRO_ATTN_PS4 || pro == PRO_ATTN_PS8 || pro == PRO_ATTN_PS12; }
+// split slots the merge prologue of `pro` reads (all of them, unconditionally)
+constexpr int ps_slots(int pro) { return pro == PRO_ATTN_PS4 ? 4 : pro == PRO_ATTN_PS8 ? 8 : pro == PRO_ATTN_PS12 ? 12 : VLM_MERGE_S; }
 constexpr int EPI_ROPE_KV = 1 << 10;   // internal epilogue id (qkv projection)
 
 struct RopeKvArgs {
@@ -57,7 +64,7 @@ struct AttnProArgs {
   const float* part_ml;      // [M][Hq][S][2]  (PRO_ATTN: m in the natural-log domain; PRO_ATTN_PS: log2 domain, -inf = no page)
   int S, Hq, D;
 };
-constexpr int AT2_S = VLM_MERGE_S;    // splits the PRO_ATTN_PS prologue reads (all of them, unconditionally)
+constexpr int AT2_S = VLM_MERGE_S;    // most splits a PRO_ATTN_PS prologue reads
 
 __device__ __forceinline__ u32x4_t ntl(const void* p) { return __builtin_nontemporal_load(reinterpret_cast<const u32x4_t*>(p)); }
 
@@ -97,7 +104,7 @@ __global__ __launch_bounds__(256) void gemv_rowwave_kernel(const bf16_t* __restr
                                                            RopeKvArgs rk, AttnProArgs ap) {
   const bf16_t* __restrict__ x = static_cast<const bf16_t*>(xsrc);
   const bf16_t* __restrict__ norm_w = static_cast<const bf16_t*>(xaux);
-  if (PRO == PRO_ATTN_PS) {
+  if (is_ps(PRO)) {
     ap.part_o = static_cast<const float*>(xsrc);
     ap.part_ml = static_cast<const float*>(xaux);
     ap.S = ldx & 255;
@@ -194,14 +201,15 @@ __global__ __launch_bounds__(256) void gemv_rowwave_kernel(const bf16_t* __restr
   // without a page carries m = -inf and is dropped by a select; its O bytes may be anything), all of it issued here, ahead
   // of the weight stream: the attention launch ends at its partial stores (no ticket, no last-arriver pass), and this
   // kernel pays S * 40 B per thread of L2 reads in front of its weights
-  float2 a2_ml[PRO == PRO_ATTN_PS ? AT2_S : 1];
-  f32x4_t a2_o[PRO == PRO_ATTN_PS ? AT2_S : 1][2];
-  if (PRO == PRO_ATTN_PS) {
+  constexpr int A2_NS = is_ps(PRO) ? ps_slots(PRO) : 1;
+  float2 a2_ml[A2_NS];
+  f32x4_t a2_o[A2_NS][2];
+  if (is_ps(PRO)) {
     const int ch = min(tid, nchunk - 1), hd0 = ch * 8;
     const size_t base = (size_t)(hd0 / ap.D) * ap.S;
     const float* po = ap.part_o;
 #pragma unroll
-    for (int sp = 0; sp < AT2_S; ++sp) {
+    for (int sp = 0; sp < A2_NS; ++sp) {
       const size_t e = base + min(sp, ap.S - 1);
       a2_ml[sp] = *reinterpret_cast<const float2*>(ap.part_ml + e * 2);
       a2_o[sp][0] = *reinterpret_cast<const f32x4_t*>(po + e * ap.D + hd0 % ap.D);
@@ -315,7 +323,7 @@ __global__ __launch_bounds__(256) void gemv_rowwave_kernel(const bf16_t* __restr
         reinterpret_cast<uint4*>(xs)[item] = o;     // item = m * nchunk + chunk: xs is [MB][K]
       }
     }
-  } else if (PRO == PRO_ATTN_PS) {
+  } else if (is_ps(PRO)) {
     // x[h*D + d] = sum_s f_s O_s[d] / sum_s f_s l_s,  f_s = 2^(m_s - M)   (attn_pagesplit.hpp)
     const uint4 o = vlm_merge_splits16(a2_ml, a2_o, ap.S);
     if (tid < nchunk) reinterpret_cast<uint4*>(smem)[tid] = o;
@@ -538,9 +546,9 @@ int launch_rw(const Args& a, int n_waves) {
   const int grid = vlm_cdiv(n_waves, 4);
   const size_t lds = (size_t)MB * a.K * 2 + (PRO == PRO_ATTN ? (size_t)MB * a.ap.Hq * a.ap.S * 2 * sizeof(float) : 0);
   // the two slots that change meaning with the prologue (see the kernel's parameter list)
-  const void* xsrc = PRO == PRO_ATTN_PS ? (const void*)a.ap.part_o : a.x;
-  const void* xaux = PRO == PRO_ATTN_PS ? (const void*)a.ap.part_ml : a.norm_w;
-  const int ldx = PRO == PRO_ATTN_PS ? (a.ap.S | a.ap.D << 8) : a.ldx;
+  const void* xsrc = is_ps(PRO) ? (const void*)a.ap.part_o : a.x;
+  const void* xaux = is_ps(PRO) ? (const void*)a.ap.part_ml : a.norm_w;
+  const int ldx = is_ps(PRO) ? (a.ap.S | a.ap.D << 8) : a.ldx;
   hipLaunchKernelGGL((gemv_rowwave_kernel<R, KC, MB, PRO, EPI>), dim3(grid), dim3(256), lds, a.st, (const bf16_t*)a.W, xsrc,
                      xaux, (const bf16_t*)a.bias, (const bf16_t*)a.res, a.N, a.K, a.ldw, ldx, (bf16_t*)a.y, a.ldy, a.ldres,
                      a.eps, a.rk, a.ap);
@@ -561,7 +569,7 @@ int launch_rw_r(const Args& a) {
   }
   // the split merge of the o_proj prologue is repeated by every workgroup: half as many of them at 4 rows per wave
   // (measured: 96 workgroups on 256 CUs lose 0.5 us per launch - profiles/decode_slack_ab.txt; A/B only)
-  if constexpr (PRO == PRO_ATTN_PS && KC <= 3)
+  if constexpr (is_ps(PRO) && KC <= 3)
     if (g_gemv_variant & 16) return launch_rw<4, KC, MB, PRO, EPI>(a, vlm_cdiv(a.N, 4));
   if (EPI == EPI_ROPE_KV) {
     const int waves = (a.rk.Hq + a.rk.Hkv) * (a.rk.D / 2) + a.rk.Hkv * a.rk.D / 2;
@@ -747,6 +755,12 @@ extern "C" int vlm_gemv_attn_out_bf16(const void* part_o, const void* part_ml, i
   if (K % 8 || K > 2048 || D % 8) return VLM_ERR_SHAPE;     // one x chunk per thread
   Args a{nullptr, Wo, nullptr, h, nullptr, h, N, K, K, K, ldh, ldh, 0.f, RopeKvArgs{},
          AttnProArgs{(const float*)part_o, (const float*)part_ml, nsplit, Hq, D}, (hipStream_t)stream};
+  // the smallest form that holds the launch's splits (variant bit 11 off: always the 16-slot form)
+  if (g_gemv_variant & 2048) {
+    if (nsplit <= 4) return launch_rw_k<1, PRO_ATTN_PS4, VLM_EPI_RESIDUAL>(a);
+    if (nsplit <= 8) return launch_rw_k<1, PRO_ATTN_PS8, VLM_EPI_RESIDUAL>(a);
+    if (nsplit <= 12) return launch_rw_k<1, PRO_ATTN_PS12, VLM_EPI_RESIDUAL>(a);
+  }
   return launch_rw_k<1, PRO_ATTN_PS, VLM_EPI_RESIDUAL>(a);
 }
 

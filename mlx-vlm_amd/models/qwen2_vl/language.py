@@ -358,12 +358,13 @@ class LanguageModel:
         self._init_pool()
 
     # decode-step tuning (results are identical under every setting up to bf16 ties; defaults from the measurements in
-    # DESIGN.md, environment overrides VLM_DECODE_<NAME> for A/B runs).  gemv_variant 525 = bits 0, 2, 3, 9 of
+    # DESIGN.md, environment overrides VLM_DECODE_<NAME> for A/B runs).  gemv_variant 2573 = bits 0, 2, 3, 9, 11 of
     # VLM_TUNE_GEMV_VARIANT: down projection at 6 rows per workgroup, gate/up and head at 2 rows per wave
     # (profiles/decode_slack_ab.txt), the partial-only attention of a one-row step over 4 workgroups per page
-    # (profiles/latency_launches_ab.txt); host_ring (tokens through a pinned ring, no copy kernel per step) measured
-    # +0.2-0.4 % in four series, under the project's bar each time: off
-    TUNING_DEFAULTS = {"fused_tail": 1, "mfma_gemv": 1, "attn_pagesplit": 16, "gemv_variant": 525, "attn_merge": 1, "host_ring": 0}
+    # (profiles/latency_launches_ab.txt), attention + o_proj of a one-row greedy step over as many splits as its context
+    # has pages, in classes of 4 (profiles/split_classes_ab.txt); host_ring (tokens through a pinned ring, no copy kernel
+    # per step) measured +0.2-0.4 % in four series, under the project's bar each time: off
+    TUNING_DEFAULTS = {"fused_tail": 1, "mfma_gemv": 1, "attn_pagesplit": 16, "gemv_variant": 2573, "attn_merge": 1, "host_ring": 0}
 
     def apply_tuning(self, **over):
         L = _lib.lib()
@@ -968,11 +969,20 @@ class LanguageModel:
         fused = bool(self.tuning.get("fused_tail")) and not hasattr(self._w["embed"], "wq")
         flags = ((_lib.DECODE_FUSED_TAIL if fused else 0) | (_lib.DECODE_WINDOW if st.window is not None else 0) |
                  (_lib.DECODE_HOST_RING if host_ring else 0))
+        # a one-row greedy step at a short context (gemv_variant bit 11): attention and o_proj over 4 / 8 / 12 splits instead of
+        # 16 - the smallest class whose splits still own at most one page each at the LAST step enqueued here (64 S >= ctx + 1;
+        # the host knows the context: every step advances it by one), so the bytes are those of 16.  Beyond 768 tokens, in a
+        # window and over the 8-bit pools nothing changes.  The class is part of the engine's graph key: one captured step each.
+        if (st.B == 1 and fused and st.window is None and not q8 and st.nsplit == 1 and (int(self.tuning["gemv_variant"]) & 2048)
+                and float(sampler_args.get("temperature", 0.0)) == 0.0):
+            split_class = (st.seqs[0].kv_entries + n_steps + 255) // 256
+            if split_class <= 3:
+                flags |= split_class << _lib.DECODE_SPLITS_SHIFT
         args = st.args(flags=flags, penalties=penalties, **sampler_args)
         if os.environ.get("VLM_NO_GRAPH"):           # diagnostics: every launch of the step visible to the HIP runtime's log
             use_graph = False
         if use_graph:
-            key = (st.seq_row0, st.nsplit, fused, bool(host_ring), q8, st.window,
+            key = (st.seq_row0, st.nsplit, fused, bool(host_ring), q8, st.window, flags & _lib.DECODE_SPLITS_MASK,
                    penalties if isinstance(penalties, str) else penalties.key() if penalties else None,
                    tuple(sorted(sampler_args.items())))
             if st.graph_key != key or getattr(self, "_graph_owner", None) is not st:
