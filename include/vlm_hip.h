@@ -130,7 +130,14 @@ int vlm_gemv_attn_out(const void* part_o, const void* part_ml, int nsplit, const
  * vlm_gemv_w4 / vlm_gemv_w4_qkv_rope_kvwrite: the decode GEMVs of vlm_gemv_bf16 / vlm_gemv_qkv_rope_kvwrite with the
  *   dequantisation fused into the operand path (fp32 affine form per group, no weight is rounded); M in {1,2,4,8}.
  * vlm_dequant_w4: rows of the matrix as bf16 (fp32 scale * q + bias, one rounding): rows == NULL -> rows 0..n_rows-1
- *   (prefill: materialised once per projection, then vlm_gemm_bf16), rows != NULL -> gather (QuantizedEmbedding lookup). */
+ *   (prefill: materialised once per projection, then vlm_gemm_bf16), rows != NULL -> gather (QuantizedEmbedding lookup).
+ *   n_table_rows == -1 is the QUANTISE direction, mx.quantize(w, group_size=64, bits=4) as `mlx_vlm.convert -q` runs it
+ *   (quant_utils.py:98-104): `out` is then the bf16 SOURCE [n_rows][K] with leading dimension ldo (ldo >= K, ldo % 8 == 0,
+ *   16-byte aligned), Wq [n_rows][K/8] and Wsb [n_rows][K/64] are WRITTEN (both contiguous) and `rows` must be NULL
+ *   (VLM_ERR_ARG otherwise).  Per group, in fp32 with IEEE division and rint: scale = max((max - min) / 15, 1e-7), signed so
+ *   that the edge of larger magnitude lands on an integer (edge = |min| > |max| ? min : max; q0 = rint(edge / scale);
+ *   scale = edge / q0 if q0 != 0; bias = edge, or 0 when q0 == 0); q = clip(rint((w - bias) / scale), 0, 15); scale and bias
+ *   are rounded to bf16 only when stored.  Non-finite weights are outside the contract (min / max skip a NaN). */
 int vlm_gemv_w4(const void* x, const void* Wq, const void* Wsb, const void* bias, const void* res, const void* norm_w, void* y,
                 int M, int N, int K, int ldx, int ldy, int ldres, float eps, int epilogue, void* stream);
 int vlm_gemv_w4_qkv_rope_kvwrite(const void* h, const void* norm_w, float eps, const void* Wq, const void* Wsb, const void* bqkv,

@@ -27,6 +27,7 @@ _LAZY = {
     "PromptCacheState": ("generate", "PromptCacheState"),
     "VisionFeatureCache": ("vision_cache", "VisionFeatureCache"),
     "APCManager": ("apc", "APCManager"),
+    "convert": ("convert", "convert"),
 }
 
 

@@ -485,6 +485,10 @@ VLM_INTERNAL int vlm_gemv_w4_qkv_rope_kvwrite_ex(const void* h, const void* norm
 
 extern "C" int vlm_dequant_w4(const void* Wq, const void* Wsb, const void* rows, void* out, int n_rows, int K, int ldo,
                               int n_table_rows, void* stream) {
+  if (n_table_rows == -1) {      // the quantise direction (include/vlm_hip.h): `out` is the bf16 source, Wq / Wsb are written
+    if (rows) return VLM_ERR_ARG;
+    return vlm_quantize_w4(out, const_cast<void*>(Wq), const_cast<void*>(Wsb), n_rows, K, ldo, stream);
+  }
   if (!Wq || !Wsb || !out || n_rows < 0 || K <= 0 || n_table_rows <= 0) return VLM_ERR_ARG;
   if (K % 64 != 0 || ldo % 8 != 0) return VLM_ERR_SHAPE;
   if (n_rows == 0) return VLM_OK;

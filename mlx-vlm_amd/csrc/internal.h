@@ -121,6 +121,10 @@ VLM_INTERNAL int vlm_top_logprobs(const void* lp, int ld, int B, int V, int K, v
 struct vlm_image_patch_args;
 VLM_INTERNAL int vlm_image_patches(const struct vlm_image_patch_args* a, void* dst, int rows, int cols, int ld_dst, void* stream);
 
+/* quantize_w4.hip: what vlm_dequant_w4 does with n_table_rows == -1 (mx.quantize(group_size = 64, bits = 4) of a bf16 matrix
+ * [n_rows][K], leading dimension ldw, into Wq [n_rows][K / 8] and Wsb [n_rows][K / 64]) */
+VLM_INTERNAL int vlm_quantize_w4(const void* w, void* Wq, void* Wsb, int n_rows, int K, int ldw, void* stream);
+
 VLM_INTERNAL int vlm_sample_last_launches(void);   /* sample.hip: kernels the last vlm_sample / vlm_sample_advance of this thread enqueued */
 
 /* sample.hip: the sampled step's tail for the engine's captured step - vlm_sample (temperature > 0; top_p / min_p / top_k) with the

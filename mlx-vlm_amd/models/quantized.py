@@ -64,6 +64,22 @@ def take(W: Dict[str, torch.Tensor], path: str) -> QuantW:
     return QuantW(wq.contiguous(), sb.to(torch.int32).contiguous())
 
 
+def split_sb(q: QuantW):
+    """the inverse of the fusing in `take`: QuantW.sb -> (scales, biases), bf16 [N, K / 64], as a checkpoint stores them.
+    Bit operations on the host only: the low and the high 16 bits of every word, viewed as bf16."""
+    halves = q.sb.cpu().contiguous().view(torch.int16).reshape(*q.sb.shape, 2)          # little endian: [..., 0] = low half
+    return halves[..., 0].contiguous().view(torch.bfloat16), halves[..., 1].contiguous().view(torch.bfloat16)
+
+
+def quantize(w: torch.Tensor, device) -> QuantW:
+    """mx.quantize(w, group_size=64, bits=4) of a bf16 matrix on the device (vlm_dequant_w4's quantise direction) ->
+    QuantW with host tensors: what `convert(quantize=True)` does to one Linear / Embedding weight"""
+    from .. import ops
+
+    wq, sb = ops.quantize_w4(w.to(device))
+    return QuantW(wq.cpu(), sb.cpu())
+
+
 def cat_rows(parts) -> QuantW:
     return QuantW(torch.cat([p.wq for p in parts], 0).contiguous(), torch.cat([p.sb for p in parts], 0).contiguous())
 

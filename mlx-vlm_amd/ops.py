@@ -708,6 +708,28 @@ def dequant_w4(wq, sb, rows=None, out=None):
     return out
 
 
+def quantize_w4(w):
+    """mx.quantize(w, group_size=64, bits=4) of a bf16 matrix [N, K] -> (wq int32 [N, K / 8], sb int32 [N, K / 64]) in the
+    engine layout dequant_w4 / gemv_w4 read (the quantise direction of vlm_dequant_w4: n_table_rows == -1)"""
+    _dev(w)
+    if w.dim() != 2 or w.dtype != torch.bfloat16:
+        raise ValueError(f"quantize_w4 takes a 2-D bfloat16 matrix, got {tuple(w.shape)} {w.dtype}")
+    N, K = w.shape
+    if K == 0 or K % 64 != 0:
+        raise ValueError(f"quantize_w4: K = {K} is not a multiple of the group size 64")
+    if w.stride(1) != 1 or w.stride(0) < K or w.stride(0) % 8 or w.data_ptr() % 16:      # the kernel reads 16 bytes per lane
+        w = w.contiguous()
+        if w.data_ptr() % 16:                 # a one-row slice is "contiguous" wherever it starts
+            w = w.clone()
+    wq = torch.empty(N, K // 8, dtype=torch.int32, device=w.device)
+    sb = torch.empty(N, K // 64, dtype=torch.int32, device=w.device)
+    if N == 0:
+        return wq, sb
+    check(_lib.lib().vlm_dequant_w4(_p(wq), _p(sb), None, _p(w), N, K, w.stride(0) if N > 1 else K, -1, _stream()),
+          "quantize_w4")
+    return wq, sb
+
+
 def gemm_set_staging(mode: int):
     """0 = automatic (LDS DMA when K % 64 == 0), 1 = always register staging (test / A-B knob)."""
     check(_lib.lib().vlm_gemm_set_staging(int(mode)), "gemm_set_staging")

@@ -86,6 +86,14 @@ def read_sanitized_weights(model_path: str, model, config: dict) -> Dict[str, to
     return {**{k: v for k, v in weights.items() if not k.startswith("vision_tower.")}, **vt}
 
 
+def sanitizer(config: dict):
+    """The family's model object for `read_sanitized_weights` alone (name and conv-layout logic): constructed on the host and
+    never given weights.  The KV pool, the captured graphs and every device tensor of an engine model come with `load_weights`,
+    which this object never sees - so `convert` reads a 7B checkpoint without allocating a page."""
+    arch, _ = get_model_and_args(config)
+    return arch.Model(arch.ModelConfig.from_dict(config), device="cpu")
+
+
 def load_model(model_path: str, lazy: bool = False, device="cuda", **kwargs):
     """reference utils.py:736-987: config -> model class -> sanitize -> load_weights."""
     config = load_config(model_path)
