@@ -232,7 +232,11 @@ int vlm_attn_decode_paged(const void* q, int ldq, const void* kpool, const void*
  * of every head writes (m, l) - m in the log2 domain, (-inf, 0) for a split with no page - to part_ml fp32
  * [B][Hq][nsplit][2] and, when it has pages, its unnormalised O as fp32 to part_o [B][Hq][nsplit][D] (ABI v8; bf16 before -
  * a rounding point the reference's fused attention does not have); the launch ends at those (plain) stores and
- * vlm_gemv_attn_out_bf16 merges them in the o_proj prologue. */
+ * vlm_gemv_attn_out_bf16 merges them in the o_proj prologue.
+ * The pitch of part_ml (added within ABI v8, the partial-only form alone): nsplit may carry P << 16, P >= nsplit - part_ml is
+ * then [B][Hq][P][2] and the pairs nsplit .. P - 1 of a head are never written.  With P even a head's pairs start on 16 bytes,
+ * which is what the exact-split forms of vlm_gemv_attn_out_bf16 read; P = 0 (every caller before): P = nsplit.  part_o keeps
+ * the pitch nsplit. */
 int vlm_attn_decode_paged_split(const void* q, int ldq, const void* kpool, const void* vpool, const void* block_table,
                                 int max_pages, const void* kv_len, int kv_len_add, int B, int Hq, int Hkv, int D,
                                 float scale, int nsplit, void* part_o, void* part_ml, void* tickets, void* out, int ldo,
@@ -283,7 +287,9 @@ int vlm_attn_prefill_paged_q8(const void* q, int ldq, void* out, int ldo, const 
 
 /* h[0][0:N] += merge(partials of vlm_attn_decode_paged_split's partial-only form) Wo^T for ONE decode row
  * (language.py:115-120,151): every thread of the o_proj GEMV loads one 8-element chunk of all nsplit <= 16 fp32 partials
- * and their (m, l) ahead of its weight stream and merges them in registers (bf16 Wo: the name).  Hq * D <= 2048. */
+ * and their (m, l) ahead of its weight stream and merges them in registers (bf16 Wo: the name).  Hq * D <= 2048.
+ * nsplit may carry the pitch P << 16 of part_ml as vlm_attn_decode_paged_split wrote it (0: P = nsplit, P <= 16); a P other
+ * than nsplit needs the exact-split forms (VLM_TUNE_GEMV_VARIANT bit 12, P even, part_ml on 16 bytes) - VLM_ERR_SHAPE otherwise. */
 int vlm_gemv_attn_out_bf16(const void* part_o, const void* part_ml, int nsplit, const void* Wo, void* h, int ldh, int N,
                            int Hq, int D, void* stream);
 
@@ -569,6 +575,18 @@ typedef struct vlm_decode_args {
                                    the same bytes (a longer context is still attended over in full - other bits).  Ignored by
                                    every other step (more rows, 8-bit pools, a window, VLM_TUNE_ATTN_MERGE 0). */
 #define VLM_DECODE_SPLITS_MASK (3 << VLM_DECODE_SPLITS_SHIFT)
+#define VLM_DECODE_NSPLITS_SHIFT 6 /* bits 6 .. 10 (added within ABI v8): S = (flags >> 6) & 31, 0 = not named.  S in 1 .. 16: the
+                                   step of VLM_DECODE_SPLITS_SHIFT runs its attention and o_proj over EXACTLY S splits - the caller
+                                   promises ctx + 1 <= 64 S for every replay, i.e. S = the pages of the longest context it will
+                                   replay the step at.  Every split owns at most one page, a split whose page the context has
+                                   not reached yet reports m = -inf and is dropped by the merge, and the live ones are added in
+                                   the order of 16 splits: the same bytes.  The attention launch starts Hkv x S x 4 workgroups
+                                   and none of them finds no page at the last replay; the o_proj prologue reads S (m, l, O)
+                                   slots and none is dead (VLM_TUNE_GEMV_VARIANT bit 12: its exact forms; part_ml then has a
+                                   per-head pitch of S rounded up to even, see vlm_attn_decode_paged_split).  Wins over the
+                                   class of bits 4, 5 when both are set; S > 16 and every step that ignores the class ignore it.
+                                   Part of the graph key like every flag: one captured step per count. */
+#define VLM_DECODE_NSPLITS_MASK (31 << VLM_DECODE_NSPLITS_SHIFT)
 
 int vlm_llm_create(const vlm_llm_config* cfg, void** handle);          /* (host) */
 int vlm_llm_destroy(void* handle);
@@ -616,11 +634,16 @@ int vlm_llm_decode_launches(void* handle);
                                        (m, l, O) slots ahead of its weights, not all 16 (dead slots are dropped by a select either
                                        way), and the Python layer asks for such launches: a one-row greedy step carries the
                                        context class of VLM_DECODE_SPLITS_SHIFT in its flags.
+                                       bit 12 (4096): vlm_gemv_attn_out_bf16 at Hq * D <= 1536 (and bit 4 off) over S splits runs a
+                                       prologue compiled for exactly S = 1 .. 16: S slots, no clamped address, and the (m, l) pairs
+                                       of a head as ceil(S / 2) 16-byte loads where part_ml has an even per-head pitch (an odd one
+                                       keeps the forms of bit 11); the Python layer names the page count of a one-row greedy
+                                       step's context in VLM_DECODE_NSPLITS_SHIFT of its flags.
                                        A row's sum does not depend on the rows its wave owns, an output tile not on the
                                        workgroup that owns it, a merge not on slots that hold no page: every bit gives the same
                                        bytes.
                                        Measured (profiles/decode_slack_ab.txt, profiles/latency_launches_ab.txt,
-                                       profiles/split_classes_ab.txt): bits 0, 2, 3, 9, 11 win - the Python layer sets 2573 - bit 4
+                                       profiles/split_classes_ab.txt, profiles/split_exact_ab.txt): bits 0, 2, 3, 9, 11, 12 win - the Python layer sets 6669 - bit 4
                                        loses 1.7 %, bit 5 changes nothing, bit 8 gains half of bit 9; bits 6, 7 and 10 are unused:
                                        a qkv form with no scalar-load wait ahead of its weights (+0.6 %, under the bar), the o_proj
                                        in three-wave workgroups (-0.7 %) and the greedy tail's log-sum-exp partials written by the

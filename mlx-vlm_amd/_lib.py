@@ -112,6 +112,7 @@ DECODE_ACT16 = 2                            # `act` holds 16 x intermediate_size
 DECODE_WINDOW = 4                           # max_kv_size on the device: ctx = [2][B] (n, w), pos = [2][B] (p, d)
 DECODE_HOST_RING = 8                        # out_ring is pinned host memory: the tail stores the token at system scope, no copy
 DECODE_SPLITS_SHIFT, DECODE_SPLITS_MASK = 4, 48  # bits 4, 5: a one-row step's attention + o_proj over 4 c splits (ctx + 1 <= 256 c)
+DECODE_NSPLITS_SHIFT, DECODE_NSPLITS_MASK = 6, 31 << 6  # bits 6..10: ... over exactly S splits (ctx + 1 <= 64 S), 0 = not named
 TUNE_MFMA_GEMV, TUNE_ATTN_PAGESPLIT, TUNE_GEMV_VARIANT, TUNE_ATTN_MERGE = 6, 7, 8, 9  # vlm_llm_set_tuning keys (include/vlm_hip.h)
 # modes of the decode step (same entry point, but these DO change what a DECODE_WINDOW step computes)
 MODE_WINDOW_SIZE, MODE_WINDOW_KEEP, MODE_WINDOW_RING_POS = 16, 17, 18

@@ -258,16 +258,17 @@ __global__ __launch_bounds__(NW * 64) void attn_decode_mfma_kernel(
 template <int G, bool MERGE>
 __device__ __forceinline__ void pagesplit_finish(f32x4_t (&ot)[8], float m_run, float l_run, int npages, int bh, int b, int g,
                                                  int s, int S, int Hkv, int lane, int ldo, float* part_o, float* part_ml,
-                                                 unsigned* tickets, bf16_t* __restrict__ out) {
+                                                 unsigned* tickets, bf16_t* __restrict__ out, int mlp) {
   const int head = lane & 15, gq = lane >> 4;
   l_run = col4_sum(l_run);
   if (!MERGE) {
     // partials for the o_proj prologue (vlm_gemv_attn_out_bf16): EVERY split writes (m, l) - a split with no page writes
     // (-inf, 0) and is skipped there - and the splits with pages their O^T as fp32 [b][head][s][d] (plain stores: the
     // kernel boundary publishes them; fp32 since round 6 - a bf16 partial is a rounding point the reference does not have).  m stays in the log2 domain of this kernel.
+    // mlp: the per-head pitch of part_ml in pairs (S, or what the caller rounded it up to: vlm_attn_decode_paged_split).
     if (head < G) {
-      const size_t e = ((size_t)b * (Hkv * G) + (g * G + head)) * S + s;
-      if (gq == 0) *reinterpret_cast<float2*>(part_ml + e * 2) = make_float2(m_run, l_run);
+      const size_t hq = (size_t)b * (Hkv * G) + (g * G + head), e = hq * S + s;
+      if (gq == 0) *reinterpret_cast<float2*>(part_ml + (hq * mlp + s) * 2) = make_float2(m_run, l_run);
       if (m_run != -INFINITY) {
         float* po = part_o + e * HD + 4 * gq;
 #pragma unroll
@@ -366,7 +367,7 @@ __global__ __launch_bounds__(64) void attn_decode_pagesplit_kernel(
   // at entry it put a full lgkmcnt(0) in front of them, and without it the tail's arguments are fetched lazily, one more
   // round trip on the path to the ticket.
   const auto args_batch = [&] {
-    // (pad_ fills the hole in front of the pointers and is "used" too: a dead dword in the middle of the batch gets its
+    // (pad_ fills the hole in front of the pointers - MERGE = false: it carries the pitch of part_ml - and is "used" too: a dead dword in the middle of the batch gets its
     //  register reused at once, and the write to it waits for the whole batch - ahead of the K / V loads again)
     asm volatile("" ::"s"(part_o), "s"(part_ml), "s"(tickets), "s"(out), "s"(kv_len_add), "s"(scale_log2), "s"(ldo), "s"(pad_));
   };
@@ -376,20 +377,21 @@ __global__ __launch_bounds__(64) void attn_decode_pagesplit_kernel(
   vlm_pagesplit_walk<G, IDENT>(q, kpool, vpool, block_table, kv_len, ldq, max_pages, Hkv, kv_len_add, scale_log2, S, b, g, s, lane, ot,
                                m_run, l_run, npages, args_batch);
 
-  pagesplit_finish<G, MERGE>(ot, m_run, l_run, npages, bh, b, g, s, S, Hkv, lane, ldo, part_o, part_ml, tickets, out);
+  pagesplit_finish<G, MERGE>(ot, m_run, l_run, npages, bh, b, g, s, S, Hkv, lane, ldo, part_o, part_ml, tickets, out, pad_);
 }
 
 // The partial-only launch with the output dimensions of a page split over DZ workgroups (grid z): every z computes the scores
 // and the softmax statistics of its pages exactly as above, and keeps 8 / DZ of the eight 16-row output tiles - their V rows,
-// their PV MFMAs, their stores.  z = 0 alone stores (m, l).  Same layout [b][head][s][d], same bytes; K is read DZ times.
+// their PV MFMAs, their stores.  z = 0 alone stores (m, l), at a per-head pitch of mlp pairs (S, or what the caller rounded it
+// up to).  Same layout [b][head][s][d], same bytes; K is read DZ times.
 template <int G, bool IDENT, int DZ>
 __global__ __launch_bounds__(64) void attn_decode_pagesplit_dz_kernel(
     const bf16_t* __restrict__ q, const bf16_t* __restrict__ kpool, const bf16_t* __restrict__ vpool,
     const int* __restrict__ block_table, const int* __restrict__ kv_len, int ldq, int max_pages, int Hkv, int S,
-    int kv_len_add, float scale_log2, float* part_o, float* part_ml) {
+    int kv_len_add, float scale_log2, float* part_o, float* part_ml, int mlp) {
   const int bh = blockIdx.x, b = bh / Hkv, g = bh % Hkv, s = blockIdx.y, z = blockIdx.z;
   const int lane = threadIdx.x, head = lane & 15, gq = lane >> 4;
-  const auto args_batch = [&] { asm volatile("" ::"s"(part_o), "s"(part_ml), "s"(kv_len_add), "s"(scale_log2)); };   // (as above)
+  const auto args_batch = [&] { asm volatile("" ::"s"(part_o), "s"(part_ml), "s"(kv_len_add), "s"(scale_log2), "s"(mlp)); };   // (as above)
   constexpr int NDT = 8 / DZ;
   f32x4_t ot[NDT];
   float m_run, l_run;
@@ -398,8 +400,8 @@ __global__ __launch_bounds__(64) void attn_decode_pagesplit_dz_kernel(
                                                          scale_log2, S, b, g, s, lane, ot, m_run, l_run, npages, args_batch, z);
   l_run = col4_sum(l_run);
   if (head < G) {
-    const size_t e = ((size_t)b * (Hkv * G) + (g * G + head)) * S + s;
-    if (gq == 0 && z == 0) *reinterpret_cast<float2*>(part_ml + e * 2) = make_float2(m_run, l_run);
+    const size_t hq = (size_t)b * (Hkv * G) + (g * G + head), e = hq * S + s;
+    if (gq == 0 && z == 0) *reinterpret_cast<float2*>(part_ml + (hq * mlp + s) * 2) = make_float2(m_run, l_run);
     if (m_run != -INFINITY) {
       float* po = part_o + e * HD + 4 * gq + 16 * NDT * z;
 #pragma unroll
@@ -687,7 +689,7 @@ __global__ __launch_bounds__(64) void attn_decode_pagesplit_q8_kernel(
     for (int r = 0; r < 4; ++r) ot[dt][r] += ob[dt >> 2];
   // (HP: 2 S splits of half pages; the active ones are s2 < ceil(len / 32))
   pagesplit_finish<G, MERGE>(ot, m_run, l_run, HP ? (len + 31) / 32 : npages, bh, b, g, s2, HP ? 2 * S : S, Hkv, lane, ldo, part_o,
-                             part_ml, tickets, out);
+                             part_ml, tickets, out, HP ? 2 * S : S);
 }
 
 __global__ __launch_bounds__(128) void attn_decode_combine_kernel(const float* __restrict__ part_o,
@@ -772,6 +774,10 @@ extern "C" int vlm_attn_decode_paged_split(const void* q, int ldq, const void* k
                                            void* tickets, void* out, int ldo, void* stream) {
   if (!q || !kpool || !vpool || !kv_len || !part_o || !part_ml || max_pages <= 0) return VLM_ERR_ARG;
   if (out && !tickets) return VLM_ERR_ARG;
+  // nsplit >> 16: the per-head pitch of part_ml in (m, l) pairs, the partial-only launch alone (vlm_hip.h); 0 = nsplit
+  const int mlp = nsplit > 0 && (nsplit >> 16) ? nsplit >> 16 : nsplit & 0xffff;
+  if (nsplit > 0) nsplit &= 0xffff;
+  if (mlp < nsplit || (mlp != nsplit && out)) return VLM_ERR_ARG;
   if (B <= 0 || Hq <= 0 || Hkv <= 0 || nsplit <= 0 || nsplit > 65535 || Hq % Hkv != 0) return VLM_ERR_ARG;
   if (D != HD || ldq % 8 != 0 || ldo % 4 != 0) return VLM_ERR_SHAPE;
   if ((size_t)B * Hq * nsplit * HD * 4 >= ((size_t)1 << 31)) return VLM_ERR_SHAPE;   // 32-bit buffer offsets
@@ -785,7 +791,7 @@ extern "C" int vlm_attn_decode_paged_split(const void* q, int ldq, const void* k
 #define GOZ1(GV, ID, DZV)                                                                                                \
   hipLaunchKernelGGL((attn_decode_pagesplit_dz_kernel<GV, ID, DZV>), gridz, dim3(64), 0, st, (const bf16_t*)q,            \
                      (const bf16_t*)kpool, (const bf16_t*)vpool, (const int*)block_table, (const int*)kv_len, ldq, max_pages, \
-                     Hkv, nsplit, kv_len_add, sl2, (float*)part_o, (float*)part_ml)
+                     Hkv, nsplit, kv_len_add, sl2, (float*)part_o, (float*)part_ml, mlp)
 #define GOZ(GV)                                                                                                          \
   do {                                                                                                                   \
     if (!block_table) { if (dz == 2) GOZ1(GV, true, 2); else GOZ1(GV, true, 4); }                                        \
@@ -811,7 +817,7 @@ extern "C" int vlm_attn_decode_paged_split(const void* q, int ldq, const void* k
 #define GO1(GV, ID, MG)                                                                                                  \
   hipLaunchKernelGGL((attn_decode_pagesplit_kernel<GV, ID, MG>), grid, dim3(64), 0, st, (const bf16_t*)q,                 \
                      (const bf16_t*)kpool, (const bf16_t*)vpool, (const int*)block_table, (const int*)kv_len, ldq, max_pages, \
-                     Hkv, nsplit, kv_len_add, sl2, ldo, 0, (float*)part_o, (float*)part_ml, (unsigned*)tickets, (bf16_t*)out)
+                     Hkv, nsplit, kv_len_add, sl2, ldo, mlp, (float*)part_o, (float*)part_ml, (unsigned*)tickets, (bf16_t*)out)
 #define GO(GV)                                                                                                           \
   do {                                                                                                                   \
     if (!block_table) { if (out) GO1(GV, true, true); else GO1(GV, true, false); }                                       \

@@ -41,7 +41,7 @@ struct DecodeGraph {
   int launches;
   unsigned long long last_use;
 };
-constexpr size_t MAX_DECODE_GRAPHS = 16;
+constexpr size_t MAX_DECODE_GRAPHS = 32;
 
 // A/B knobs of the captured step (vlm_llm_set_tuning; measured defaults)
 struct Tuning {
@@ -430,7 +430,15 @@ static int decode_impl(Llm* m, const vlm_decode_args* a, void* stream, int* laun
     // splits every split owns at most one page, as under 16): the attention launches fewer workgroups, the o_proj prologue
     // reads fewer dead (m, l, O) slots in front of its weights (gemv_bf16.hip PRO_ATTN_PS4 / 8 / 12), the bytes are the same
     const int split_class = (a->flags & VLM_DECODE_SPLITS_MASK) >> VLM_DECODE_SPLITS_SHIFT;
-    if (split_class && merge_in_oproj && !q8 && !(a->flags & VLM_DECODE_WINDOW) && 4 * split_class < psplit) psplit = 4 * split_class;
+    // ... or over exactly the splits the caller's context has pages (VLM_DECODE_NSPLITS_SHIFT: 1 .. 16, wins over the class):
+    // no workgroup of the attention launch finds no page, no slot of the prologue is dead (PRO_ATTN_PS_BASE + S), and where
+    // the o_proj has that form the (m, l) pairs of a head sit at an even pitch, read 16 bytes at a time
+    const int split_exact = (a->flags & VLM_DECODE_NSPLITS_MASK) >> VLM_DECODE_NSPLITS_SHIFT;
+    int ml_pitch = 0;
+    if (split_exact && merge_in_oproj && !q8 && !(a->flags & VLM_DECODE_WINDOW) && a->nsplit == 1 && split_exact <= psplit) {
+      psplit = split_exact;
+      if (vlm_gemv_attn_out_exact_ok(Hq * hd) && (uintptr_t)a->part_ml % 16 == 0) ml_pitch = ((psplit + 1) & ~1) << 16;
+    } else if (split_class && merge_in_oproj && !q8 && !(a->flags & VLM_DECODE_WINDOW) && 4 * split_class < psplit) psplit = 4 * split_class;
     if (q8) {
       const size_t lo = (size_t)i * m->kv.layer_stride;                   // elements == bytes of the u8 pools
       TRY(vlm_attn_decode_paged_q8(a->qkv, QKV, kp, vp, off(m->kv.kpool8, lo), off(m->kv.vpool8, lo),
@@ -439,7 +447,7 @@ static int decode_impl(Llm* m, const vlm_decode_args* a, void* stream, int* laun
                                    merge_in_oproj ? nullptr : a->attn, Hq * hd, 1, stream)); ++n;
     } else if (psplit) {
       TRY(vlm_attn_decode_paged_split(a->qkv, QKV, kp, vp, m->kv.block_table, m->kv.max_pages, a->ctx, 1, B, Hq, Hkv, hd, scale,
-                                      psplit, a->part_o, a->part_ml, m->attn_tickets, merge_in_oproj ? nullptr : a->attn,
+                                      psplit | ml_pitch, a->part_o, a->part_ml, m->attn_tickets, merge_in_oproj ? nullptr : a->attn,
                                       Hq * hd, stream)); ++n;
     } else if (a->nsplit == 1) {
       // short contexts: one workgroup per (sequence, kv head) -> final bf16 vector, plain o_proj GEMV + residual
@@ -466,7 +474,7 @@ static int decode_impl(Llm* m, const vlm_decode_args* a, void* stream, int* laun
       continue;
     }
     if (merge_in_oproj) {
-      TRY(vlm_gemv_attn_out_bf16(a->part_o, a->part_ml, psplit, w.wo, a->h, D, D, Hq, hd, stream)); ++n;
+      TRY(vlm_gemv_attn_out_bf16(a->part_o, a->part_ml, psplit | ml_pitch, w.wo, a->h, D, D, Hq, hd, stream)); ++n;
     } else if (psplit || a->nsplit == 1 || combine) {
       TRY(lin_gemv(m, a->attn, w.wo, w.wo_sb, nullptr, a->h, nullptr, a->h, B, D, Hq * hd, D, D, 0.f, VLM_EPI_RESIDUAL, stream)); ++n;
     } else {

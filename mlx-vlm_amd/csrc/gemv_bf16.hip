@@ -37,12 +37,21 @@ namespace {
 // PRO_ATTN_PS4 / 8 / 12: PRO_ATTN_PS reading 4 / 8 / 12 split slots instead of VLM_MERGE_S = 16 (a launch over S splits takes the
 // smallest form that holds them: the slots >= S are dropped by a select, so every form gives the bytes of PRO_ATTN_PS, and a
 // short context does not pay 40 B per thread and dead slot in front of the weight stream)
+// PRO_ATTN_PS_BASE + NS, NS = 1 .. 16 (variant bit 12): PRO_ATTN_PS over EXACTLY NS splits - the launch's split count is the
+// template's, so no slot is dead, no address is clamped, and a head's (m, l) pairs - contiguous in part_ml - arrive as
+// ceil(NS / 2) 16-byte loads at a per-head pitch the caller rounded up to even (the pair behind an odd NS is loaded and never
+// used).  The merge adds the splits in the same order over the same values: the bytes of PRO_ATTN_PS.
 enum { PRO_NONE = 0, PRO_RMSNORM = 1, PRO_ATTN = 2, PRO_ATTN_PS = 3, PRO_RMSNORM_1W = 4, PRO_ATTN_PS4 = 5, PRO_ATTN_PS8 = 6,
-       PRO_ATTN_PS12 = 7 };
+       PRO_ATTN_PS12 = 7, PRO_ATTN_PS_BASE = 16 };
 constexpr bool is_norm(int pro) { return pro == PRO_RMSNORM || pro == PRO_RMSNORM_1W; }
-constexpr bool is_ps(int pro) { return pro == PRO_ATTN_PS || pro == PRO_ATTN_PS4 || pro == PRO_ATTN_PS8 || pro == PRO_ATTN_PS12; }
+constexpr bool ps_exact(int pro) { return pro > PRO_ATTN_PS_BASE && pro <= PRO_ATTN_PS_BASE + VLM_MERGE_S; }
+constexpr bool is_ps(int pro) {
+  return pro == PRO_ATTN_PS || pro == PRO_ATTN_PS4 || pro == PRO_ATTN_PS8 || pro == PRO_ATTN_PS12 || ps_exact(pro);
+}
 // split slots the merge prologue of `pro` reads (all of them, unconditionally)
-constexpr int ps_slots(int pro) { return pro == PRO_ATTN_PS4 ? 4 : pro == PRO_ATTN_PS8 ? 8 : pro == PRO_ATTN_PS12 ? 12 : VLM_MERGE_S; }
+constexpr int ps_slots(int pro) {
+  return ps_exact(pro) ? pro - PRO_ATTN_PS_BASE : pro == PRO_ATTN_PS4 ? 4 : pro == PRO_ATTN_PS8 ? 8 : pro == PRO_ATTN_PS12 ? 12 : VLM_MERGE_S;
+}
 constexpr int EPI_ROPE_KV = 1 << 10;   // internal epilogue id (qkv projection)
 
 struct RopeKvArgs {
@@ -92,7 +101,8 @@ __device__ __forceinline__ float dot8(const u32x4_t w, const u32x4_t x, float ac
 // the prologue (the launcher fills them, unpacked below):
 //   xsrc   x [M][ldx] bf16                      | PRO_ATTN_PS: the attention's partial O, fp32 (AttnProArgs::part_o)
 //   xaux   norm_w [K] bf16 (norm prologues)     | PRO_ATTN_PS: its (m, l) pairs (AttnProArgs::part_ml)
-//   ldx    leading dimension of x               | PRO_ATTN_PS: S | D << 8 (x has no leading dimension: it is the merge)
+//   ldx    leading dimension of x               | PRO_ATTN_PS: S | D << 8 (x has no leading dimension: it is the merge);
+//                                               | the exact forms: | P << 24, the per-head pitch of part_ml in (m, l) pairs
 // PRO_ATTN (the general merge) keeps reading AttnProArgs.  The qkv form (EPI_ROPE_KV) needs 22 dwords ahead of its weight
 // stream - these plus pos, slot, inv_freq, (Hq, Hkv, D) and long_from of RopeKvArgs: its x / norm_w loads go out on the
 // preloaded arguments and the rest waits for the scalar load behind them (profiles/kernarg_preload.txt).
@@ -108,7 +118,7 @@ __global__ __launch_bounds__(256) void gemv_rowwave_kernel(const bf16_t* __restr
     ap.part_o = static_cast<const float*>(xsrc);
     ap.part_ml = static_cast<const float*>(xaux);
     ap.S = ldx & 255;
-    ap.D = ldx >> 8;
+    ap.D = ps_exact(PRO) ? (ldx >> 8) & 0xffff : ldx >> 8;
   }
   extern __shared__ __attribute__((aligned(16))) char smem[];   // xs[MB][K] bf16
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -202,9 +212,23 @@ __global__ __launch_bounds__(256) void gemv_rowwave_kernel(const bf16_t* __restr
   // of the weight stream: the attention launch ends at its partial stores (no ticket, no last-arriver pass), and this
   // kernel pays S * 40 B per thread of L2 reads in front of its weights
   constexpr int A2_NS = is_ps(PRO) ? ps_slots(PRO) : 1;
+  // the exact forms: ap.S == A2_NS by the launcher, the head's pairs as 16-byte loads at pitch P (even, >= A2_NS)
+  constexpr int A2_NQ = ps_exact(PRO) ? (A2_NS + 1) / 2 : 1;
   float2 a2_ml[A2_NS];
+  f32x4_t a2_mlq[A2_NQ];
   f32x4_t a2_o[A2_NS][2];
-  if (is_ps(PRO)) {
+  if constexpr (ps_exact(PRO)) {
+    const int ch = min(tid, nchunk - 1), hd0 = ch * 8, hh = hd0 / ap.D;
+    const float* pml = ap.part_ml + (size_t)hh * (ldx >> 24) * 2;
+    const float* po = ap.part_o + (size_t)hh * A2_NS * ap.D + hd0 % ap.D;
+#pragma unroll
+    for (int q = 0; q < A2_NQ; ++q) a2_mlq[q] = *reinterpret_cast<const f32x4_t*>(pml + 4 * q);
+#pragma unroll
+    for (int sp = 0; sp < A2_NS; ++sp) {
+      a2_o[sp][0] = *reinterpret_cast<const f32x4_t*>(po + (size_t)sp * ap.D);
+      a2_o[sp][1] = *reinterpret_cast<const f32x4_t*>(po + (size_t)sp * ap.D + 4);
+    }
+  } else if (is_ps(PRO)) {
     const int ch = min(tid, nchunk - 1), hd0 = ch * 8;
     const size_t base = (size_t)(hd0 / ap.D) * ap.S;
     const float* po = ap.part_o;
@@ -325,7 +349,11 @@ __global__ __launch_bounds__(256) void gemv_rowwave_kernel(const bf16_t* __restr
     }
   } else if (is_ps(PRO)) {
     // x[h*D + d] = sum_s f_s O_s[d] / sum_s f_s l_s,  f_s = 2^(m_s - M)   (attn_pagesplit.hpp)
-    const uint4 o = vlm_merge_splits16(a2_ml, a2_o, ap.S);
+    if constexpr (ps_exact(PRO)) {
+#pragma unroll
+      for (int sp = 0; sp < A2_NS; ++sp) a2_ml[sp] = make_float2(a2_mlq[sp >> 1][2 * (sp & 1)], a2_mlq[sp >> 1][2 * (sp & 1) + 1]);
+    }
+    const uint4 o = vlm_merge_splits16(a2_ml, a2_o, ps_exact(PRO) ? A2_NS : ap.S);
     if (tid < nchunk) reinterpret_cast<uint4*>(smem)[tid] = o;
   } else if (PRO == PRO_ATTN) {
     // general form (more splits / rows): three short phases so that every global load of a phase is independent
@@ -548,7 +576,7 @@ int launch_rw(const Args& a, int n_waves) {
   // the two slots that change meaning with the prologue (see the kernel's parameter list)
   const void* xsrc = is_ps(PRO) ? (const void*)a.ap.part_o : a.x;
   const void* xaux = is_ps(PRO) ? (const void*)a.ap.part_ml : a.norm_w;
-  const int ldx = is_ps(PRO) ? (a.ap.S | a.ap.D << 8) : a.ldx;
+  const int ldx = is_ps(PRO) ? (a.ap.S | a.ap.D << 8 | (ps_exact(PRO) ? a.ldx << 24 : 0)) : a.ldx;   // (exact forms: a.ldx = P)
   hipLaunchKernelGGL((gemv_rowwave_kernel<R, KC, MB, PRO, EPI>), dim3(grid), dim3(256), lds, a.st, (const bf16_t*)a.W, xsrc,
                      xaux, (const bf16_t*)a.bias, (const bf16_t*)a.res, a.N, a.K, a.ldw, ldx, (bf16_t*)a.y, a.ldy, a.ldres,
                      a.eps, a.rk, a.ap);
@@ -569,7 +597,7 @@ int launch_rw_r(const Args& a) {
   }
   // the split merge of the o_proj prologue is repeated by every workgroup: half as many of them at 4 rows per wave
   // (measured: 96 workgroups on 256 CUs lose 0.5 us per launch - profiles/decode_slack_ab.txt; A/B only)
-  if constexpr (is_ps(PRO) && KC <= 3)
+  if constexpr (is_ps(PRO) && !ps_exact(PRO) && KC <= 3)
     if (g_gemv_variant & 16) return launch_rw<4, KC, MB, PRO, EPI>(a, vlm_cdiv(a.N, 4));
   if (EPI == EPI_ROPE_KV) {
     const int waves = (a.rk.Hq + a.rk.Hkv) * (a.rk.D / 2) + a.rk.Hkv * a.rk.D / 2;
@@ -642,6 +670,10 @@ int launch_sk_m(int M, const Args& a) {
 }  // namespace
 
 VLM_INTERNAL void vlm_gemv_set_variant(int bits) { g_gemv_variant = bits; }
+
+// does vlm_gemv_attn_out_bf16 take its exact-split forms at K = Hq * D?  (variant bit 12; 2 rows per wave and one x chunk per
+// thread at K <= 1536 only: bit 4 and wider rows keep the class forms)  The engine asks before it pads the pitch of part_ml.
+VLM_INTERNAL int vlm_gemv_attn_out_exact_ok(int K) { return (g_gemv_variant & 4096) && !(g_gemv_variant & 16) && K <= 512 * 3; }
 
 extern "C" int vlm_gemv_bf16(const void* x, const void* W, const void* bias, const void* res, const void* norm_w,
                              void* y, int M, int N, int K, int ldx, int ldw, int ldy, int ldres, float eps,
@@ -750,11 +782,25 @@ VLM_INTERNAL int vlm_gemv_qkv_rope_kvwrite_ex(const void* h, const void* norm_w,
 
 extern "C" int vlm_gemv_attn_out_bf16(const void* part_o, const void* part_ml, int nsplit, const void* Wo, void* h, int ldh,
                                       int N, int Hq, int D, void* stream) {
-  if (!part_o || !part_ml || !Wo || !h || nsplit <= 0 || nsplit > AT2_S) return VLM_ERR_ARG;
+  // nsplit >> 16: the per-head pitch P of part_ml in (m, l) pairs, 0 = nsplit (vlm_hip.h)
+  const int pitch = nsplit > 0 && (nsplit >> 16) ? nsplit >> 16 : nsplit & 0xffff;
+  nsplit &= 0xffff;
+  if (!part_o || !part_ml || !Wo || !h || nsplit <= 0 || nsplit > AT2_S || pitch < nsplit || pitch > AT2_S) return VLM_ERR_ARG;
   const int K = Hq * D;
   if (K % 8 || K > 2048 || D % 8) return VLM_ERR_SHAPE;     // one x chunk per thread
   Args a{nullptr, Wo, nullptr, h, nullptr, h, N, K, K, K, ldh, ldh, 0.f, RopeKvArgs{},
          AttnProArgs{(const float*)part_o, (const float*)part_ml, nsplit, Hq, D}, (hipStream_t)stream};
+  // exactly the launch's splits (variant bit 12): the pairs of a head are read 16 bytes at a time, so the pitch must be even
+  // and part_ml 16-byte aligned; any other launch takes the forms below, which know the plain pitch only
+  if (vlm_gemv_attn_out_exact_ok(K) && pitch % 2 == 0 && (uintptr_t)part_ml % 16 == 0) {
+    a.ldx = pitch;
+    switch (nsplit) {
+#define GO(NS) case NS: return launch_rw_r<3, 1, PRO_ATTN_PS_BASE + NS, VLM_EPI_RESIDUAL>(a)
+      GO(1); GO(2); GO(3); GO(4); GO(5); GO(6); GO(7); GO(8); GO(9); GO(10); GO(11); GO(12); GO(13); GO(14); GO(15); GO(16);
+#undef GO
+    }
+  }
+  if (pitch != nsplit) return VLM_ERR_SHAPE;
   // the smallest form that holds the launch's splits (variant bit 11 off: always the 16-slot form)
   if (g_gemv_variant & 2048) {
     if (nsplit <= 4) return launch_rw_k<1, PRO_ATTN_PS4, VLM_EPI_RESIDUAL>(a);

@@ -358,13 +358,14 @@ class LanguageModel:
         self._init_pool()
 
     # decode-step tuning (results are identical under every setting up to bf16 ties; defaults from the measurements in
-    # DESIGN.md, environment overrides VLM_DECODE_<NAME> for A/B runs).  gemv_variant 2573 = bits 0, 2, 3, 9, 11 of
+    # DESIGN.md, environment overrides VLM_DECODE_<NAME> for A/B runs).  gemv_variant 6669 = bits 0, 2, 3, 9, 11, 12 of
     # VLM_TUNE_GEMV_VARIANT: down projection at 6 rows per workgroup, gate/up and head at 2 rows per wave
     # (profiles/decode_slack_ab.txt), the partial-only attention of a one-row step over 4 workgroups per page
     # (profiles/latency_launches_ab.txt), attention + o_proj of a one-row greedy step over as many splits as its context
-    # has pages, in classes of 4 (profiles/split_classes_ab.txt); host_ring (tokens through a pinned ring, no copy kernel
+    # has pages, in classes of 4 (profiles/split_classes_ab.txt) and, up to 1024 tokens, over exactly that many
+    # (profiles/split_exact_ab.txt); host_ring (tokens through a pinned ring, no copy kernel
     # per step) measured +0.2-0.4 % in four series, under the project's bar each time: off
-    TUNING_DEFAULTS = {"fused_tail": 1, "mfma_gemv": 1, "attn_pagesplit": 16, "gemv_variant": 2573, "attn_merge": 1, "host_ring": 0}
+    TUNING_DEFAULTS = {"fused_tail": 1, "mfma_gemv": 1, "attn_pagesplit": 16, "gemv_variant": 6669, "attn_merge": 1, "host_ring": 0}
 
     def apply_tuning(self, **over):
         L = _lib.lib()
@@ -978,11 +979,20 @@ class LanguageModel:
             split_class = (st.seqs[0].kv_entries + n_steps + 255) // 256
             if split_class <= 3:
                 flags |= split_class << _lib.DECODE_SPLITS_SHIFT
+        # ... or over exactly as many splits as that context has pages (gemv_variant bit 12, up to 1024 tokens; the engine lets
+        # the count win over the class): no attention workgroup without a page, no dead slot ahead of the o_proj's weights.  A
+        # run of steps that crosses a page boundary takes the count of its last step - the page the first ones do not reach
+        # yet reports m = -inf and is dropped.  One captured step per count, cached in the engine across requests.
+        if (st.B == 1 and fused and st.window is None and not q8 and st.nsplit == 1 and (int(self.tuning["gemv_variant"]) & 4096)
+                and float(sampler_args.get("temperature", 0.0)) == 0.0):
+            n_pages = (st.seqs[0].kv_entries + n_steps + 63) // 64
+            if n_pages <= 16:
+                flags |= n_pages << _lib.DECODE_NSPLITS_SHIFT
         args = st.args(flags=flags, penalties=penalties, **sampler_args)
         if os.environ.get("VLM_NO_GRAPH"):           # diagnostics: every launch of the step visible to the HIP runtime's log
             use_graph = False
         if use_graph:
-            key = (st.seq_row0, st.nsplit, fused, bool(host_ring), q8, st.window, flags & _lib.DECODE_SPLITS_MASK,
+            key = (st.seq_row0, st.nsplit, fused, bool(host_ring), q8, st.window, flags & (_lib.DECODE_SPLITS_MASK | _lib.DECODE_NSPLITS_MASK),
                    penalties if isinstance(penalties, str) else penalties.key() if penalties else None,
                    tuple(sorted(sampler_args.items())))
             if st.graph_key != key or getattr(self, "_graph_owner", None) is not st:

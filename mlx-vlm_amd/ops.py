@@ -248,18 +248,20 @@ def attn_decode_paged(q, kpool, vpool, block_table, kv_len, kv_len_add, Hq, Hkv,
 
 
 def gemv_attn_out_bf16_(part_o, part_ml, wo, h, Hq, D):
-    """h[0] += merge(page-split partials) @ wo.T in place (one decode row)"""
+    """h[0] += merge(page-split partials) @ wo.T in place (one decode row).  part_ml may have a wider per-head pitch than
+    part_o has splits (attn_decode_paged_split(ml_pitch=...)): the library's exact-split forms read it."""
     _dev(part_o, part_ml, wo, h)
-    check(_lib.lib().vlm_gemv_attn_out_bf16(_p(part_o), _p(part_ml), part_o.shape[2], _p(wo), _p(h), h.stride(0), wo.shape[0],
+    nsplit, pitch = part_o.shape[2], part_ml.shape[2]
+    check(_lib.lib().vlm_gemv_attn_out_bf16(_p(part_o), _p(part_ml), nsplit | (pitch << 16 if pitch != nsplit else 0), _p(wo), _p(h), h.stride(0), wo.shape[0],
                                             Hq, D, _stream()), "gemv_attn_out_bf16")
     return h
 
 
 def attn_decode_paged_split(q, kpool, vpool, block_table, kv_len, kv_len_add, Hq, Hkv, D, scale, nsplit, out=None,
-                            max_pages=None, tickets=None, merge=True, part=None):
+                            max_pages=None, tickets=None, merge=True, part=None, ml_pitch=None):
     """page-split decode attention (one wave per page stride).  merge=True: the last arriver merges -> bf16 [B, Hq*D];
     merge=False: the partial-only form -> (part_o fp32 [B, Hq, nsplit, D], part_ml fp32 [B, Hq, nsplit, 2]) for
-    gemv_attn_out_bf16_."""
+    gemv_attn_out_bf16_; ml_pitch >= nsplit: part_ml is [B, Hq, ml_pitch, 2] (the pairs behind nsplit stay unwritten)."""
     _dev(q, kpool, vpool, block_table, kv_len)
     B = q.shape[0]
     if not merge:
@@ -267,10 +269,14 @@ def attn_decode_paged_split(q, kpool, vpool, block_table, kv_len, kv_len_add, Hq
             part_o, part_ml = part
         else:
             part_o = torch.full((B, Hq, nsplit, D), float("nan"), dtype=torch.float32, device=q.device)   # unwritten = NaN on purpose
-            part_ml = torch.empty(B, Hq, nsplit, 2, dtype=torch.float32, device=q.device)
+            part_ml = torch.empty(B, Hq, ml_pitch or nsplit, 2, dtype=torch.float32, device=q.device)
+        pitch = int(ml_pitch or nsplit)
+        if pitch < nsplit or part_ml.numel() < B * Hq * pitch * 2:
+            raise ValueError("attn_decode_paged_split: part_ml holds ml_pitch >= nsplit pairs per head")
         check(_lib.lib().vlm_attn_decode_paged_split(_p(q), q.stride(0), _p(kpool), _p(vpool), _p(block_table),
                                                      block_table.shape[1] if block_table is not None else int(max_pages),
-                                                     _p(kv_len), kv_len_add, B, Hq, Hkv, D, scale, nsplit, _p(part_o),
+                                                     _p(kv_len), kv_len_add, B, Hq, Hkv, D, scale,
+                                                     nsplit | (pitch << 16 if pitch != nsplit else 0), _p(part_o),
                                                      _p(part_ml), None, None, 0, _stream()), "attn_decode_split")
         return part_o, part_ml
     part_o = torch.empty(B, Hq, nsplit, D, dtype=torch.float32, device=q.device)

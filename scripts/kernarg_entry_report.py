@@ -44,6 +44,11 @@ KERNELS = [
 ALTERNATES = [
     ("attention attn_decode_pagesplit_kernel<6,true,false>  (bits 8, 9 off)", "attn_decode", r"attn_decode_pagesplit_kernelILi6ELb1ELb0EE"),
     ("attention attn_decode_pagesplit_dz_kernel<6,true,2>  (bit 8)", "attn_decode", r"attn_decode_pagesplit_dz_kernelILi6ELb1ELi2EE"),
+    # the forms the o_proj launch takes under bits 11, 12: a class of 4, and exactly S splits (PRO_ATTN_PS_BASE + S; an even
+    # and an odd count - the odd one loads a pair it never uses)
+    ("o_proj    gemv_rowwave_kernel<2,3,1,6,8>  (bit 11, 8 slots)", "gemv_bf16", r"gemv_rowwave_kernelILi2ELi3ELi1ELi6ELi8EE"),
+    ("o_proj    gemv_rowwave_kernel<2,3,1,24,8>  (bit 12, 8 splits)", "gemv_bf16", r"gemv_rowwave_kernelILi2ELi3ELi1ELi24ELi8EE"),
+    ("o_proj    gemv_rowwave_kernel<2,3,1,25,8>  (bit 12, 9 splits)", "gemv_bf16", r"gemv_rowwave_kernelILi2ELi3ELi1ELi25ELi8EE"),
 ]
 
 
