@@ -40,6 +40,11 @@ def _to_np(x):
     return np.asarray(x)
 
 
+def dense(x):
+    """a 4-bit matrix materialised as bf16 for a GEMM (the prompt-chunk path); anything else as it is"""
+    return ops.dequant_w4(x.wq, x.sb) if hasattr(x, "wq") else x
+
+
 class DecodeState:
     """Device-resident state of a batch of B decoding sequences (what one graph replay reads/writes)."""
 
@@ -555,27 +560,36 @@ class LanguageModel:
         self._keep = (h, xn, qkv, attn, act, xlast, pos_d, meta, rows_d)  # keep alive until the stream has run
         return logits
 
+    def _layer_weights(self, i):
+        """layer i's weights by the names of self._w; of a 4-bit model only THIS layer's matrices are dequantised"""
+        if not self.quantized:
+            return self._w
+        return {k: dense(v) for k, v in self._w.items() if k.startswith(f"{i}.")}
+
     def _prefill_onto_cache(self, inputs_embeds, position_ids, caches, lengths, logits_rows, reserve_extra, paged_attn=False):
-        """A prompt chunk appended to a NON-EMPTY cache: chunked prefill (reference ar.py:426-472) and `prompt_cache=`
-        continuation across calls, i.e. multi-turn (dispatch.py:861-882, common.py:243-263).  The chunk's queries attend
-        to [cached tokens | the chunk] (cache.py:345-367 + base.py:366-373 with the causal mask offset by the cache
-        length).  Kept simple: the layer loop runs here over the C-ABI operators; per layer the cached k / v rows are fetched
-        back into a full-length token-major buffer (vlm_kv_gather) and the varlen causal attention runs with the segment's
-        query rows starting at the cache length (vlm_attn_prefill's q_start, round 6: the prefix rows are keys only - they used
-        to carry zero queries, O(Tf^2) per chunk).
-        paged_attn (the warm admission of the prefix cache, batch.py: the admission path of every warm request, not a rare one):
-        no gather and no full-length buffer - the chunk's rows attend over the bf16 pages in place (ops.attn_prefill_paged, the
-        bf16 twin of the 8-bit branch below), whatever the chunk's length.  bf16 caches and 128-wide heads only."""
+        """A prompt chunk appended to a NON-EMPTY cache: chunked prefill (reference ar.py:426-472), `prompt_cache=` continuation
+        across calls, i.e. multi-turn (dispatch.py:861-882, common.py:243-263), a chunk onto a QuantizedKVCache (an update of any
+        length, then quantized_scaled_dot_product_attention: cache.py:233-334, base.py:260-302) and the warm admission of the
+        prefix cache (batch.py: the admission path of every warm request, not a rare one).  The chunk's queries attend to
+        [cached tokens | the chunk] under the causal mask offset by the cache length (cache.py:345-367, base.py:366-373).
+        The layer loop runs here over the C-ABI operators: per layer the chunk's K / V go into the pages (mrope_kvwrite_), then
+        the chunk's rows attend by ONE of five routes, decided once:
+
+          route      taken for                          the chunk's rows attend
+          paged      paged_attn=True, any length        over the bf16 pages in place (attn_prefill_paged; bf16, 128-wide heads)
+          q8_decode  an 8-bit cache, a short chunk      as decode rows over the 8-bit pages (attn_decode_paged_q8)
+          q8_paged   an 8-bit cache, a longer chunk     over the 8-bit pages in place (attn_prefill_paged_q8)
+          decode     a bf16 cache, a short chunk        as decode rows over the pages (attn_decode_paged)
+          gather     everything else                    over a full-length copy [prefix | chunk] (kv_gather_ + attn_prefill)
+
+        A short chunk: up to 64 new tokens in all (VLM_ONTO_CACHE_DECODE_ATTN=0: none is).  The 8-bit routes first turn the
+        layer's new tokens 8-bit (kv_quantize_tokens); only `gather` builds anything of the full length."""
         if any(c[0]._seq.rotating for c in caches):
             raise NotImplementedError("max_kv_size: a multi-token update of a non-empty rotating cache (the reference first trims "
                                       "the window to max_size - 1 + S, cache.py:486-505) is not built; only the first prompt")
-        t, dev = self.args, self.device
+        t, dev, pool = self.args, self.device, self.pool
         hd, Hq, Hkv = self.head_dim, t.num_attention_heads, t.num_key_value_heads
-        D, QKV = t.hidden_size, (Hq + 2 * Hkv) * self.head_dim
         seqs = [c[0]._seq for c in caches]
-        # sequences whose cache is a QuantizedKVCache: the chunk's tokens are quantised layer by layer as they are written and the
-        # attention reads the 8-bit pools (vlm_attn_prefill_paged_q8) - QuantizedKVCache.update_and_fetch with an update of any
-        # length, then quantized_scaled_dot_product_attention under the offset causal mask (cache.py:233-334, base.py:260-302).
         # A mix of 8-bit and bf16 sequences is refused as in decode_run
         if len({bool(s.q8) for s in seqs}) > 1:
             raise RuntimeError("a prompt chunk cannot mix sequences with and without a quantized KV cache")
@@ -586,158 +600,107 @@ class LanguageModel:
         offs = [int(s.offset) for s in seqs]
         for n, s in zip(lengths, seqs):
             s.reserve(s.offset + n + reserve_extra)
-        pool = self.pool
-        bt = pool.block_table
-        bf, i32 = torch.bfloat16, torch.int32
-        T = int(sum(lengths))
-        tot = [o + n for o, n in zip(offs, lengths)]
-        cu_full = np.concatenate([[0], np.cumsum(tot)]).astype(np.int32)
-        Tf = int(cu_full[-1])
-        pos = np.ascontiguousarray(position_ids, dtype=np.int32)
-        pos_d = _lib.h2d(pos, dev)
+        T, S = int(sum(lengths)), len(seqs)
+        short = T <= 64 and os.environ.get("VLM_ONTO_CACHE_DECODE_ATTN") != "0"
         if paged_attn:
-            # no full-length buffer: what the layer loop needs is where the chunk's own K / V go and the segments of the launch
             if q8 or hd != 128:
                 raise NotImplementedError("paged_attn: the paged prefill attention is built for bf16 caches with 128-wide heads")
-            cu_new = np.concatenate([[0], np.cumsum(lengths)]).astype(np.int32)
-            meta = _lib.h2d(np.concatenate([np.concatenate([np.full(n, s.seq, np.int32) for n, s in zip(lengths, seqs)]),
-                                            np.concatenate([o + np.arange(n, dtype=np.int32) for o, n in zip(offs, lengths)]),
-                                            cu_new, np.asarray([s.seq for s in seqs], dtype=np.int32),
-                                            np.asarray(offs, dtype=np.int32)]).astype(np.int32), dev)
-            S_ = len(seqs)
-            new_seq_d, new_slot_d = meta[:T], meta[T:2 * T]
-            pg_cu_d, pg_seq_d, pg_start_d = meta[2 * T:2 * T + S_ + 1], meta[2 * T + S_ + 1:2 * T + 2 * S_ + 1], meta[2 * T + 2 * S_ + 1:]
-            pg_nqb = int(sum((n + ops.PAGED_PREFILL_QBLOCK - 1) // ops.PAGED_PREFILL_QBLOCK for n in lengths))
-            return self._onto_cache_layers_paged(inputs_embeds, pos_d, lengths, seqs, logits_rows, new_seq_d, new_slot_d, pg_cu_d,
-                                                 pg_seq_d, pg_start_d, pg_nqb)
-        # rows of the full-length buffer: per sequence [prefix | chunk]
-        new_rows = np.concatenate([np.arange(cu_full[i] + offs[i], cu_full[i + 1]) for i in range(len(seqs))]).astype(np.int64)
-        old_rows = np.concatenate([np.arange(cu_full[i], cu_full[i] + offs[i]) for i in range(len(seqs))]).astype(np.int64)
-        full_seq = np.concatenate([np.full(tot[i], seqs[i].seq, np.int32) for i in range(len(seqs))])
-        full_slot = np.concatenate([np.arange(tot[i], dtype=np.int32) for i in range(len(seqs))])
-        new_rows_d, old_rows_d = _lib.h2d(new_rows, dev), _lib.h2d(old_rows, dev)
-        seq_d, slot_d, cu_d = _lib.h2d(full_seq, dev), _lib.h2d(full_slot, dev), _lib.h2d(cu_full, dev)
-        new_seq_d, new_slot_d = seq_d[new_rows_d], slot_d[new_rows_d]
-        old_seq_d, old_slot_d = seq_d[old_rows_d].contiguous(), slot_d[old_rows_d].contiguous()
-        nqb = int(sum((n + 127) // 128 for n in lengths))      # query blocks: the chunk rows only
-        qstart_d = _lib.h2d(np.asarray(offs, dtype=np.int32), dev)
-        if os.environ.get("VLM_ONTO_CACHE_QSTART") == "0":     # A/B knob: the form of rounds 3-5 (the prefix rows carry zero queries)
-            nqb, qstart_d = int(sum((n + 127) // 128 for n in tot)), None
-        scale = float(getattr(t, "attn_scale", 0.0) or 0.0) or hd ** -0.5
-        # A SHORT chunk (a conversation turn of up to 64 tokens in all) takes the paged DECODE attention instead: every new token is
-        # a decode row over its sequence's pages with kv_len = cache length + its index + 1 (its K / V are in the pages by then:
-        # mrope_kvwrite_ below) - no gather of the prefix at all, and the keys are split over workgroups as in a decode step
-        # (one 64-row query block per head walking 16k keys took ~0.4 ms per layer; profiles/r06_long_prompt_prefill.txt).
-        # (8-bit sequences too: rows of vlm_attn_decode_paged_q8 over the 8-bit pages, the chunk's tokens quantised first.  One wave of
-        #  vlm_attn_prefill_paged_q8 walks all the keys of its 16 rows, the decode rows split them over workgroups: 46 against 156 us
-        #  at 32 rows onto 4096 tokens, profiles/q8_prefill_attn.txt)
-        short = T <= 64 and os.environ.get("VLM_ONTO_CACHE_DECODE_ATTN") != "0"
-        if q8:
-            cu_new_d = _lib.h2d(np.concatenate([[0], np.cumsum(lengths)]).astype(np.int32), dev)
-            seg_seq_d = _lib.h2d(np.asarray([s.seq for s in seqs], dtype=np.int32), dev)
-            nqb8 = int(sum((n + ops.Q8_PREFILL_QBLOCK - 1) // ops.Q8_PREFILL_QBLOCK for n in lengths))
-            new_seq_c, new_slot_c = new_seq_d.contiguous(), new_slot_d.contiguous()
-            q8_start_d = _lib.h2d(np.asarray(offs, dtype=np.int32), dev)
-        if short:
-            row_seq = np.concatenate([np.full(n, s.seq, np.int64) for n, s in zip(lengths, seqs)])
-            row_len = np.concatenate([o + 1 + np.arange(n) for o, n in zip(offs, lengths)]).astype(np.int32)
-            bt_rows = bt[_lib.h2d(row_seq, dev)].contiguous()
-            row_len_d = _lib.h2d(row_len, dev)
-            longest = int(row_len.max())
-            dec_nsplit = 1 if longest <= 2048 else max(2, min(32, (longest + 16 * PAGE - 1) // (16 * PAGE)))
-        h = inputs_embeds.contiguous().clone()
-        sec = self.mrope_section
-        def dense(x):        # 4-bit matrices are materialised as bf16 for the GEMMs of this (rare) path
-            return ops.dequant_w4(x.wq, x.sb) if hasattr(x, "wq") else x
+            route = "paged"
+        elif q8:
+            route = "q8_decode" if short else "q8_paged"
+        else:
+            route = "decode" if short else "gather"
 
-        for i in range(t.num_hidden_layers):
-            # only THIS layer's matrices are dequantised here (the head once, after the loop)
-            w = {k: (dense(v) if k.startswith(f"{i}.") else v) for k, v in self._w.items()
-                 if k.startswith(f"{i}.") or k in ("inv_freq", "norm")} if self.quantized else self._w
-            kp, vp = pool.kpool[i], pool.vpool[i]          # this layer's K / V pools (flat views)
-            xn = ops.rmsnorm(h, w[f"{i}.ln1"], t.rms_norm_eps)
-            qkv = ops.gemm(xn, w[f"{i}.wqkv"], bias=w[f"{i}.bqkv"], epilogue=ops.EPI_BIAS)
-            inv_tab = w["inv_freq"][hd // 2:] if getattr(self, "_prefill_rope_long", False) else w["inv_freq"]   # SuScaledRoPE regime of this call
-            ops.mrope_kvwrite_(qkv, Hq, Hkv, hd, pos_d[0], pos_d[1], pos_d[2], inv_tab, int(sec[0]), int(sec[1]),
-                               kv_seq=new_seq_d.contiguous(), kv_slot=new_slot_d.contiguous(), block_table=bt, kpool=kp, vpool=vp,
-                               qk_scale=getattr(t, "rope_qk_scale", None))
-            if q8:
-                # QuantizedKVCache.update_and_fetch: this layer's new rows become 8-bit, then the chunk attends over the 8-bit
-                # pages of [cached tokens | itself] in place - no full-length buffer, no gather
-                k8, v8, ksb, vsb = pool.kpool8[i], pool.vpool8[i], pool.ksb[i], pool.vsb[i]
-                ops.kv_quantize_tokens(kp, vp, k8, v8, ksb, vsb, new_seq_c, new_slot_c, bt, Hkv, hd)
-                if short:
-                    attn = ops.attn_decode_paged_q8(qkv, kp, vp, k8, v8, ksb, vsb, bt_rows, row_len_d, 0, Hq, Hkv, hd, scale, dec_nsplit,
-                                                    quantize_new=False)
-                else:
-                    attn = ops.attn_prefill_paged_q8(qkv, k8, v8, ksb, vsb, bt, seg_seq_d, cu_new_d, q8_start_d, nqb8, Hq, Hkv, hd, scale)
-                h = ops.gemm(attn, w[f"{i}.wo"], res=h, epilogue=ops.EPI_RESIDUAL)
-                xn = ops.rmsnorm(h, w[f"{i}.ln2"], t.rms_norm_eps)
-                act = ops.gemm(xn, w[f"{i}.wgu"], epilogue=ops.EPI_SWIGLU)
-                h = ops.gemm(act, w[f"{i}.wdown"], res=h, epilogue=ops.EPI_RESIDUAL)
-                continue
-            if short:
-                attn = ops.attn_decode_paged(qkv, kp, vp, bt_rows, row_len_d, 0, Hq, Hkv, hd, scale, dec_nsplit)
-                h = ops.gemm(attn, w[f"{i}.wo"], res=h, epilogue=ops.EPI_RESIDUAL)
-                xn = ops.rmsnorm(h, w[f"{i}.ln2"], t.rms_norm_eps)
-                act = ops.gemm(xn, w[f"{i}.wgu"], epilogue=ops.EPI_SWIGLU)
-                h = ops.gemm(act, w[f"{i}.wdown"], res=h, epilogue=ops.EPI_RESIDUAL)
-                continue
-            full = (torch.empty if qstart_d is not None else torch.zeros)(Tf, QKV, dtype=bf, device=dev)       # (q_start: the q columns of the prefix rows are never read)
-            full[new_rows_d] = qkv
-            if old_rows.size:
-                # ONE gather over every row of the buffer, straight into it: the chunk's rows re-read from the pages what
-                # mrope_kvwrite_ just stored there (the same bits) - no prefix buffer, no second copy of Tf rows
-                ops.kv_gather_(full, Hq, Hkv, hd, slot_d, bt, kp, vp, kv_seq=seq_d)
-            attn = ops.attn_prefill(full, full[:, Hq * hd:], full[:, (Hq + Hkv) * hd:], cu_d, nqb, Hq, Hkv, hd, scale, True,
-                                    q_start=qstart_d)
-            h = ops.gemm(attn[new_rows_d].contiguous(), w[f"{i}.wo"], res=h, epilogue=ops.EPI_RESIDUAL)
-            xn = ops.rmsnorm(h, w[f"{i}.ln2"], t.rms_norm_eps)
-            act = ops.gemm(xn, w[f"{i}.wgu"], epilogue=ops.EPI_SWIGLU)
-            h = ops.gemm(act, w[f"{i}.wdown"], res=h, epilogue=ops.EPI_RESIDUAL)
-        cu_new = np.concatenate([[0], np.cumsum(lengths)])
-        rows = (cu_new[1:] - 1) if logits_rows == "last" else np.arange(T)
-        xl = ops.rmsnorm(h[_lib.h2d(rows.astype(np.int64), dev)].contiguous(), self._w["norm"], t.rms_norm_eps)
-        logits = ops.gemm(xl, dense(self._w["head"]))[:, : t.vocab_size]
-        for n, s in zip(lengths, seqs):
-            s.offset += n
-        return logits
-
-    def _onto_cache_layers_paged(self, inputs_embeds, pos_d, lengths, seqs, logits_rows, new_seq_d, new_slot_d, cu_d, seg_seq_d,
-                                 q_start_d, nqb):
-        """The layer loop of `_prefill_onto_cache(paged_attn=True)`: per layer the chunk's K / V go into the pages
-        (mrope_kvwrite_) and its rows attend over [cached prefix | chunk] in place (ops.attn_prefill_paged) - no gather, no
-        full-length buffer, no row scatter.  4-bit matrices are materialised per layer as in the gather form."""
-        t, dev, pool = self.args, self.device, self.pool
-        hd, Hq, Hkv = self.head_dim, t.num_attention_heads, t.num_key_value_heads
+        # every route: where the chunk's K / V go (new_seq, new_slot) and the segments of the launch, in ONE upload
         bt = pool.block_table
-        T = int(sum(lengths))
+        seg_seq = np.asarray([s.seq for s in seqs], dtype=np.int32)
+        new_slot = np.concatenate([o + np.arange(n, dtype=np.int32) for o, n in zip(offs, lengths)])
+        cu_new = np.concatenate([[0], np.cumsum(lengths)])
+        pos_d = _lib.h2d(np.ascontiguousarray(position_ids, dtype=np.int32), dev)
+        meta = _lib.h2d(np.concatenate([np.repeat(seg_seq, lengths), new_slot, cu_new, seg_seq, offs]).astype(np.int32), dev)
+        new_seq_d, new_slot_d, cu_new_d, seg_seq_d, q_start_d = meta.split([T, T, S + 1, S, S])
         scale = float(getattr(t, "attn_scale", 0.0) or 0.0) or hd ** -0.5
-        sec = self.mrope_section
+
+        def pools8(i, kp, vp):
+            """QuantizedKVCache.update_and_fetch: layer i's new rows become 8-bit -> its 8-bit pools"""
+            p8 = pool.kpool8[i], pool.vpool8[i], pool.ksb[i], pool.vsb[i]
+            ops.kv_quantize_tokens(kp, vp, *p8, new_seq_d, new_slot_d, bt, Hkv, hd)
+            return p8
+
+        if route == "paged":
+            nqb = int(sum((n + ops.PAGED_PREFILL_QBLOCK - 1) // ops.PAGED_PREFILL_QBLOCK for n in lengths))
+
+            def attend(i, qkv, kp, vp):
+                return ops.attn_prefill_paged(qkv, kp, vp, bt, seg_seq_d, cu_new_d, q_start_d, nqb, Hq, Hkv, hd, scale)
+        elif route == "q8_paged":
+            nqb8 = int(sum((n + ops.Q8_PREFILL_QBLOCK - 1) // ops.Q8_PREFILL_QBLOCK for n in lengths))
+
+            def attend(i, qkv, kp, vp):
+                return ops.attn_prefill_paged_q8(qkv, *pools8(i, kp, vp), bt, seg_seq_d, cu_new_d, q_start_d, nqb8, Hq, Hkv, hd, scale)
+        elif route in ("decode", "q8_decode"):
+            # every new token is a decode row over its sequence's pages with kv_len = cache length + its index + 1 (its K / V
+            # are in the pages by then) - no gather of the prefix, and the keys are split over workgroups as in a decode step
+            # (one 64-row query block per head walking 16k keys took ~0.4 ms per layer; profiles/r06_long_prompt_prefill.txt.
+            # 8-bit: one wave of vlm_attn_prefill_paged_q8 walks all the keys of its 16 rows, the decode rows split them: 46
+            # against 156 us at 32 rows onto 4096 tokens, profiles/q8_prefill_attn.txt)
+            bt_rows = bt[new_seq_d.long()].contiguous()
+            row_len_d = new_slot_d + 1
+            longest = max(o + n for o, n in zip(offs, lengths))
+            dec_nsplit = 1 if longest <= 2048 else max(2, min(32, (longest + 16 * PAGE - 1) // (16 * PAGE)))
+
+            if q8:
+                def attend(i, qkv, kp, vp):
+                    return ops.attn_decode_paged_q8(qkv, kp, vp, *pools8(i, kp, vp), bt_rows, row_len_d, 0, Hq, Hkv, hd, scale,
+                                                    dec_nsplit, quantize_new=False)
+            else:
+                def attend(i, qkv, kp, vp):
+                    return ops.attn_decode_paged(qkv, kp, vp, bt_rows, row_len_d, 0, Hq, Hkv, hd, scale, dec_nsplit)
+        else:
+            # gather: per layer the cached k / v rows are fetched back into a token-major buffer of per sequence [prefix | chunk]
+            # rows and the varlen causal attention runs with each segment's query rows starting at its cache length (q_start:
+            # the prefix rows are keys only)
+            tot = [o + n for o, n in zip(offs, lengths)]
+            cu_full = np.concatenate([[0], np.cumsum(tot)])
+            Tf, QKV = int(cu_full[-1]), (Hq + 2 * Hkv) * hd
+            new_rows_d = _lib.h2d(np.concatenate([np.arange(cu_full[i] + offs[i], cu_full[i + 1]) for i in range(S)]).astype(np.int64),
+                                  dev)
+            full_slot = np.concatenate([np.arange(n, dtype=np.int32) for n in tot])
+            seq_d, slot_d, cu_d = _lib.h2d(np.concatenate([np.repeat(seg_seq, tot), full_slot, cu_full]).astype(np.int32),
+                                           dev).split([Tf, Tf, S + 1])
+            nqb, q_start = int(sum((n + 127) // 128 for n in lengths)), q_start_d      # query blocks: the chunk rows only
+            if os.environ.get("VLM_ONTO_CACHE_QSTART") == "0":     # A/B knob: the form of rounds 3-5 (the prefix rows carry zero queries)
+                nqb, q_start = int(sum((n + 127) // 128 for n in tot)), None
+            new_full = torch.empty if q_start is not None else torch.zeros      # (q_start: the q columns of the prefix rows are never read)
+
+            def attend(i, qkv, kp, vp):
+                full = new_full(Tf, QKV, dtype=torch.bfloat16, device=dev)
+                full[new_rows_d] = qkv
+                if Tf > T:
+                    # ONE gather over every row of the buffer, straight into it: the chunk's rows re-read from the pages what
+                    # mrope_kvwrite_ just stored there (the same bits) - no prefix buffer, no second copy of Tf rows
+                    ops.kv_gather_(full, Hq, Hkv, hd, slot_d, bt, kp, vp, kv_seq=seq_d)
+                attn = ops.attn_prefill(full, full[:, Hq * hd:], full[:, (Hq + Hkv) * hd:], cu_d, nqb, Hq, Hkv, hd, scale, True,
+                                        q_start=q_start)
+                return attn[new_rows_d].contiguous()
+
         h = inputs_embeds.contiguous().clone()
-
-        def dense(x):
-            return ops.dequant_w4(x.wq, x.sb) if hasattr(x, "wq") else x
-
-        inv_tab = self._w["inv_freq"][hd // 2:] if getattr(self, "_prefill_rope_long", False) else self._w["inv_freq"]
+        sec = self.mrope_section
+        inv_tab = self._w["inv_freq"][hd // 2:] if getattr(self, "_prefill_rope_long", False) else self._w["inv_freq"]   # SuScaledRoPE regime of this call
         qk_scale = getattr(t, "rope_qk_scale", None)
         for i in range(t.num_hidden_layers):
-            w = {k: (dense(v) if k.startswith(f"{i}.") else v) for k, v in self._w.items()
-                 if k.startswith(f"{i}.") or k in ("inv_freq", "norm")} if self.quantized else self._w
-            kp, vp = pool.kpool[i], pool.vpool[i]
+            w = self._layer_weights(i)
+            kp, vp = pool.kpool[i], pool.vpool[i]          # this layer's K / V pools (flat views)
             xn = ops.rmsnorm(h, w[f"{i}.ln1"], t.rms_norm_eps)
             qkv = ops.gemm(xn, w[f"{i}.wqkv"], bias=w[f"{i}.bqkv"], epilogue=ops.EPI_BIAS)
             ops.mrope_kvwrite_(qkv, Hq, Hkv, hd, pos_d[0], pos_d[1], pos_d[2], inv_tab, int(sec[0]), int(sec[1]), kv_seq=new_seq_d,
                                kv_slot=new_slot_d, block_table=bt, kpool=kp, vpool=vp, qk_scale=qk_scale)
-            attn = ops.attn_prefill_paged(qkv, kp, vp, bt, seg_seq_d, cu_d, q_start_d, nqb, Hq, Hkv, hd, scale)
-            h = ops.gemm(attn, w[f"{i}.wo"], res=h, epilogue=ops.EPI_RESIDUAL)
+            h = ops.gemm(attend(i, qkv, kp, vp), w[f"{i}.wo"], res=h, epilogue=ops.EPI_RESIDUAL)
             xn = ops.rmsnorm(h, w[f"{i}.ln2"], t.rms_norm_eps)
             act = ops.gemm(xn, w[f"{i}.wgu"], epilogue=ops.EPI_SWIGLU)
             h = ops.gemm(act, w[f"{i}.wdown"], res=h, epilogue=ops.EPI_RESIDUAL)
-        cu_new = np.concatenate([[0], np.cumsum(lengths)])
         rows = (cu_new[1:] - 1) if logits_rows == "last" else np.arange(T)
         xl = ops.rmsnorm(h[_lib.h2d(rows.astype(np.int64), dev)].contiguous(), self._w["norm"], t.rms_norm_eps)
-        logits = ops.gemm(xl, dense(self._w["head"]))[:, : t.vocab_size]
+        logits = ops.gemm(xl, dense(self._w["head"]))[:, : t.vocab_size]      # (the head is dequantised once, here)
         for n, s in zip(lengths, seqs):
             s.offset += n
         return logits
