@@ -375,6 +375,30 @@ int vlm_sample(const void* logits, int ld, int B, int V, void* logprobs, void* s
  * HIGHER index first; +0.0 and -0.0 are equal values; the value written is the row's own bits at that index.  NaN is outside the
  * contract.  Every other field, `scratch`, `ldlp`, `workspace` and `step_ptr` are ignored (workspace may be NULL and is not
  * touched).  One launch, one workgroup per row. */
+/* input_is_logprobs bit 2 = VLM_SAMPLE_ROW_TABLE (added within ABI v8; combinable with 1 = "log-probs in", which then holds for
+ * every row): ROW-TABLE mode - every row is drawn with its OWN sampler.  Every scalar field of the block is then ignored (a
+ * filter outside the three below switched on - typical_p, top_n_sigma, p_less, xtc_probability - is VLM_ERR_ARG), `step_ptr` is
+ * ignored, `scratch` is required, and row b reads its LINE of eight 32-bit words from the workspace the caller already owns:
+ *     word VLM_SAMPLE_ROW_LINE_WORD + b * VLM_SAMPLE_ROW_STRIDE_WORDS of the workspace (as uint32 [])
+ *     = {temperature f32, top_p f32, min_p f32, top_k i32, seed u32, count u32, T(1 - top_p) f32, T(log(min_p)) f32}
+ * - eight control words of the row's own workspace block that no other mode reads or writes, at the same place whatever the
+ * call's B (a step over the first B' < B rows of a state finds the same words) and inside vlm_sample_workspace_bytes(B) as it
+ * always was.  The last two words are the two scalar conversions of the scalar path made by whoever writes the line:
+ * (float) of the double 1 - top_p, resp. of the double log(min_p), rounded to bf16 (nearest even) and stored as f32.
+ * temperature == 0 - an all-zero line, what a workspace zero-filled by a caller that never heard of the mode holds - is a GREEDY
+ * row: argmax of the row's log-probs, lowest index on ties, no filter, no noise.  Otherwise top_p -> min_p (min_tokens_to_keep
+ * = 1) -> top_k -> categorical(logprobs / temperature), each filter off at the values that switch it off above (top_p outside
+ * (0, 1), min_p == 0, top_k <= 0 or >= V), the draw keyed (seed, count, 0, index): the row index does not enter, so a request's
+ * draws depend on its own line alone.  The call's last launch does count += 1 on every row; the host writes count = 0 when a
+ * request takes the row.  Row b gives the token, the log-prob row and (a filter on) the filtered scratch row of the scalar call
+ * on that row alone (B = 1) with the line's scalars, seed and *step_ptr = count, bit for bit (tests/test_row_sampler_gpu.py).
+ * The launches depend on (B, V, leading dimensions, alignment) only, never on the lines: lse partials, [log-probs], then the split
+ * chain (histogram, crossing, count, mask + draw) where V % 8 == 0, V >= 8192 and the rows are 16-byte aligned, else the
+ * one-workgroup filter and the Gumbel partials, then the pick - a captured call replays over any table.  scratch is written for
+ * every row (an unfiltered copy where the row has no filter). */
+#define VLM_SAMPLE_ROW_TABLE 4
+#define VLM_SAMPLE_ROW_STRIDE_WORDS 65920 /* 32-bit words from one row's workspace block to the next */
+#define VLM_SAMPLE_ROW_LINE_WORD 65928    /* 32-bit word of the workspace where row 0's line starts (32-byte aligned) */
 typedef struct vlm_sampler_params {
   double temperature, top_p, min_p;
   int min_tokens_to_keep, top_k;
@@ -386,7 +410,8 @@ typedef struct vlm_sampler_params {
   void* sort_workspace;
   unsigned seed;
   int input_is_logprobs; /* temperature > 0: `logits` already holds log-probs (what the reference hands a sampler closure,
-                            ar.py:368-379): no logsumexp pass, `logprobs` may be NULL.  2: top_logprobs mode, see above */
+                            ar.py:368-379): no logsumexp pass, `logprobs` may be NULL.  2: top_logprobs mode, see above.
+                            bit 2 (VLM_SAMPLE_ROW_TABLE, | 1 allowed): row-table mode, see above */
 } vlm_sampler_params;
 size_t vlm_sample_sort_workspace_bytes(int B, int V);
 int vlm_sample_ex(const void* logits, int ld, int B, int V, void* logprobs, void* scratch, int ldlp, void* tok, void* workspace,
@@ -587,6 +612,14 @@ typedef struct vlm_decode_args {
                                    class of bits 4, 5 when both are set; S > 16 and every step that ignores the class ignore it.
                                    Part of the graph key like every flag: one captured step per count. */
 #define VLM_DECODE_NSPLITS_MASK (31 << VLM_DECODE_NSPLITS_SHIFT)
+#define VLM_DECODE_ROW_SAMPLER (1 << 11) /* bit 11 (added within ABI v8): the step's tail samples in ROW-TABLE mode (see
+                                   VLM_SAMPLE_ROW_TABLE at vlm_sampler_params): row b draws with the line of row b in sample_ws, which
+                                   the host rewrites as requests join and leave while the captured step keeps its arguments;
+                                   temperature / top_p / min_p / top_k / seed of the args are ignored, `logprobs` and `scratch` are
+                                   required.  With VLM_DECODE_FUSED_TAIL the sampler's last launch also does vlm_decode_advance and
+                                   the next step's embedding gather (B <= 64), and bumps every row's count; without it the advance
+                                   is a launch of its own.  Part of what a cached decode graph is keyed by (the flags are).
+                                   Together with VLM_DECODE_WINDOW: an argument error, nothing is enqueued. */
 
 int vlm_llm_create(const vlm_llm_config* cfg, void** handle);          /* (host) */
 int vlm_llm_destroy(void* handle);

@@ -72,6 +72,9 @@ class SamplerParams(C.Structure):
 
 
 SAMPLE_MODE_TOP_LOGPROBS = 2      # vlm_sampler_params.input_is_logprobs: the call lists the top_k best log-probs per row (ABI v8)
+SAMPLE_MODE_ROW_TABLE = 4         # ... bit 2 (| 1: log-probs in): every row draws with its own line of the workspace (VLM_SAMPLE_ROW_TABLE)
+SAMPLE_ROW_STRIDE_WORDS = 65920   # VLM_SAMPLE_ROW_STRIDE_WORDS: 32-bit words between the workspace blocks of two rows
+SAMPLE_ROW_LINE_WORD = 65928      # VLM_SAMPLE_ROW_LINE_WORD: where row 0's line of eight words starts
 TOP_LOGPROBS_MAX_K = 64           # the kernel's cap on K (csrc/top_logprobs.hip)
 
 
@@ -113,6 +116,7 @@ DECODE_WINDOW = 4                           # max_kv_size on the device: ctx = [
 DECODE_HOST_RING = 8                        # out_ring is pinned host memory: the tail stores the token at system scope, no copy
 DECODE_SPLITS_SHIFT, DECODE_SPLITS_MASK = 4, 48  # bits 4, 5: a one-row step's attention + o_proj over 4 c splits (ctx + 1 <= 256 c)
 DECODE_NSPLITS_SHIFT, DECODE_NSPLITS_MASK = 6, 31 << 6  # bits 6..10: ... over exactly S splits (ctx + 1 <= 64 S), 0 = not named
+DECODE_ROW_SAMPLER = 1 << 11                # the tail samples in row-table mode: row b with its own line of sample_ws
 TUNE_MFMA_GEMV, TUNE_ATTN_PAGESPLIT, TUNE_GEMV_VARIANT, TUNE_ATTN_MERGE = 6, 7, 8, 9  # vlm_llm_set_tuning keys (include/vlm_hip.h)
 # modes of the decode step (same entry point, but these DO change what a DECODE_WINDOW step computes)
 MODE_WINDOW_SIZE, MODE_WINDOW_KEEP, MODE_WINDOW_RING_POS = 16, 17, 18

@@ -43,6 +43,7 @@ _PROCS_KEY = "__logits_processors__"     # a request's LogitsProcessors spec ins
 _PYPROCS_KEY = "__py_logits_processors__"   # ... its Python callables (tokens, logits) -> logits (eager steps)
 _BUDGET_KEY = "__thinking_budget_criteria__"   # ... its ThinkingBudgetCriteria
 _MASKPROC_KEY = "__mask_logits_processor__"    # ... its mask processor (structured.py: prepare_next_token_mask), captured steps
+_SAMPLER_KEY = "__sampler__"                   # ... its own sample_utils.Sampler (insert(..., samplers=)); absent: the generator's
 MAX_ROWS = 16         # default widest decode step: one N tile of the skinny-M MFMA GEMM (csrc/gemv_mfma.hip), bf16 or 4-bit weights
 WIDE_ROWS = 64        # on request (completion_batch_size > 16): WIDE steps of 32 / 64 rows on the prefill GEMMs (engine.hip decode_impl:
                       # 192.6 us per Qwen2-VL-7B layer at 32 rows, 210 at 64, against 120 per 16-row step - profiles/r03_mfma_shapes.txt)
@@ -154,7 +155,18 @@ class BatchGenerator:
     blocks are copied into its pages, only the suffix is embedded (no ViT call) and prefilled onto them, its queries attending
     straight over the pages (ops.attn_prefill_paged); after every admission the prompts' new full blocks are stored.  One manager
     may serve several generators of one model; `close()` leaves it open.  Not with kv_bits.  Speculative drafts are outside the
-    built path and are rejected."""
+    built path and are rejected.
+
+    Per-request samplers (`insert(..., samplers=)`; the reference's server hands the whole batch the sampler of whichever
+    request opened it): from the first insert that names one, every step samples in ROW-TABLE mode - row r draws with its own
+    line of the state's sampler workspace (temperature, top-p, min-p, top-k, seed and a draw counter; ops.sample_row_table),
+    written when the request takes the row, moved with it, zeroed when it leaves - inside the captured step, whose launches
+    do not depend on the lines.  What a seeded request can rely on: its n-th draw is keyed by (its seed, n, token index) -
+    neither its row nor the generator's step counter enters - so GIVEN THE SAME LOG-PROB ROWS its tokens do not depend on the
+    row it was given or on its neighbours, and a greedy request stays greedy whoever shares the batch.  The log-prob rows
+    themselves come from different GEMV forms at different batch widths, so token equality of a whole run across widths (or
+    against the request run alone) is not promised.  A generator that never sees `samplers` keeps the one shared sampler, its
+    (seed, step, row, index) key and the launches it always had."""
 
     @dataclass
     class Response:
@@ -242,6 +254,7 @@ class BatchGenerator:
             self._py_sampler, sampler = sampler, None
         self.sampler = sampler or make_sampler()
         self._sargs = self.sampler.engine_args()
+        self._row_sampling = False                    # row-table steps: set by the first insert(..., samplers=) that names a sampler
         crit = getattr(self.tokenizer, "stopping_criteria", None)
         self._stop = set(getattr(crit, "eos_token_ids", ()) or ())
         self._stop.update(int(t) for t in (stop_tokens or ()))
@@ -301,6 +314,16 @@ class BatchGenerator:
     def _new_decode_state(self, cap: int):
         return self._borrow_state(self.lm, cap)
 
+    def _sampler_lines(self) -> torch.Tensor:
+        """int32 [cap, 8]: the rows' sampler lines of the row-table steps (engine hook: a view of the state's sampler workspace;
+        a state without one - a mock engine - gets a host table)"""
+        ws = getattr(self._st, "sample_ws", None)
+        if ws is not None:
+            return ops.sample_row_table(ws)
+        if getattr(self, "_host_lines", None) is None:
+            self._host_lines = torch.zeros(self._st.B, 8, dtype=torch.int32)
+        return self._host_lines
+
     def _prefill_cold(self, batch):
         """One ViT call over all images of `batch`, one varlen prefill launch onto empty caches.
         -> (caches, lengths, logits of the last rows [n, V], rope deltas)"""
@@ -310,7 +333,7 @@ class BatchGenerator:
         ids_l = [b[1] for b in batch]
         pix_l = [b[3].get("pixel_values") for b in batch]
         grid_l = [b[3].get("image_grid_thw") for b in batch]
-        extras = [{k: v for k, v in b[3].items() if k not in ("pixel_values", "image_grid_thw", _PROCS_KEY, _PYPROCS_KEY, _BUDGET_KEY, _MASKPROC_KEY)}
+        extras = [{k: v for k, v in b[3].items() if k not in ("pixel_values", "image_grid_thw", _PROCS_KEY, _PYPROCS_KEY, _BUDGET_KEY, _MASKPROC_KEY, _SAMPLER_KEY)}
                   for b in batch]
         emb, pos, lens, deltas = embed_requests(self.model, ids_l, pix_l, grid_l, extras)
         caches = []
@@ -440,6 +463,10 @@ class BatchGenerator:
         if self._py_sampler is not None:
             _, lp = ops.sample(logits, want_logprobs=True, temperature=0.0)
             tok0 = self._call_sampler(lp)
+        elif self._row_sampling:
+            # every request's first token with its own line at count 0; the steps of its row go on from count 1 (_admit_join)
+            lines = np.stack([self._sampler_of(b).row_line(0) for b in batch])
+            tok0, lp = ops.sample_rows(logits, h2d(lines, logits.device), want_logprobs=True)
         else:
             tok0, lp = ops.sample(logits, step=step0, want_logprobs=self._want_rows(), **self._sargs)
         # top_logprobs_k > 0: the first tokens' log-prob rows stay here for `_prefill_top_logprobs`, which `_admit_begin` calls
@@ -518,7 +545,7 @@ class BatchGenerator:
         self.lm.decode_step_rows(self._st, width, self._table, self._sargs, use_graph=self.use_graph,
                                  with_logprobs=self._want_rows(),
                                  row_penalties=any(row.procs or row.mask_proc is not None for row in self._rows),
-                                 q8=self.kv_bits is not None)
+                                 q8=self.kv_bits is not None, **({"row_sampler": True} if self._row_sampling else {}))
 
     @staticmethod
     def _call_proc(proc, tokens, logits_row, last_token=None):
@@ -557,6 +584,8 @@ class BatchGenerator:
             _, lp = ops.sample(logits, want_logprobs=True, temperature=0.0)
             tok = torch.zeros(width, dtype=torch.int32, device=logits.device)
             tok[:n].copy_(self._call_sampler(lp[:n]))
+        elif self._row_sampling:
+            tok, lp = ops.sample_rows(logits, ws=st.sample_ws)      # the rows' lines where the captured step reads them; counts advance
         else:
             tok, lp = ops.sample(logits, step=st.step, want_logprobs=self._want_rows(), **self._sargs)
         st.tok[:width].copy_(tok)
@@ -622,10 +651,12 @@ class BatchGenerator:
 
     # ------------------------------------------------------------------ queue (reference ar.py:2584-2670)
     def insert(self, prompts, max_tokens=None, prompt_kwargs: Optional[List[dict]] = None, logits_processors=None,
-               thinking_budget_criteria=None) -> List[int]:
+               thinking_budget_criteria=None, samplers=None) -> List[int]:
         """logits_processors: one entry per prompt (reference ar.py:2584-2606) - None, a `sample_utils.LogitsProcessors`
         (what `make_logits_processors` returns here) or a list holding one; they run on the device inside the step, each
-        row with its own parameters and token history."""
+        row with its own parameters and token history.
+        samplers: one entry per prompt - None (the generator's sampler) or a `sample_utils.Sampler` (`make_sampler`) with
+        temperature, top_p, min_p, top_k and seed of its own; see the class docstring for what a seeded request can rely on."""
         if max_tokens is None or isinstance(max_tokens, int):
             max_tokens = [max_tokens or self.max_tokens] * len(prompts)
         if prompt_kwargs is None:
@@ -638,6 +669,17 @@ class BatchGenerator:
             raise ValueError("Insufficient number of thinking_budget_criteria provided")
         if len(max_tokens) != len(prompts) or len(prompt_kwargs) != len(prompts) or len(logits_processors) != len(prompts):
             raise ValueError("max_tokens / prompt_kwargs / logits_processors must have one entry per prompt")
+        if samplers is None:
+            samplers = [None] * len(prompts)
+        if len(samplers) != len(prompts):
+            raise ValueError("samplers must have one entry per prompt")
+        for s in samplers:
+            if s is not None and (not isinstance(s, Sampler) or s.extended):
+                raise NotImplementedError("insert(samplers=): a per-request sampler is a sample_utils.Sampler with top_p, min_p "
+                                          "(min_tokens_to_keep = 1) and top_k - the three filters a row-table line carries; the "
+                                          "extended filters and Python callables go to BatchGenerator(sampler=)")
+        if any(s is not None for s in samplers) and self._py_sampler is not None:
+            raise NotImplementedError("insert(samplers=) on a generator whose sampler is a Python callable or an extended Sampler")
         from .sample_utils import HIST_CAP, LogitsProcessors
         from .structured import is_mask_processor
         specs, pys, mps = [], [], []
@@ -666,7 +708,10 @@ class BatchGenerator:
             specs.append(sp[0] if sp else None)
             pys.append(py or None)
         uids = []
-        for p, m, kw, sp, py, crit, mp in zip(prompts, max_tokens, prompt_kwargs, specs, pys, thinking_budget_criteria, mps):
+        if any(s is not None for s in samplers) and not self._row_sampling:
+            self._begin_row_sampling()
+        for p, m, kw, sp, py, crit, mp, smp in zip(prompts, max_tokens, prompt_kwargs, specs, pys, thinking_budget_criteria, mps,
+                                                   samplers):
             ids = np.asarray(p, dtype=np.int64).reshape(-1)
             if ids.size == 0:
                 raise ValueError("empty prompt")
@@ -679,6 +724,8 @@ class BatchGenerator:
                 kw[_MASKPROC_KEY] = mp
             if crit is not None:
                 kw[_BUDGET_KEY] = crit
+            if smp is not None:
+                kw[_SAMPLER_KEY] = smp
             self._unprocessed_sequences.append((self.uid_count, ids, int(m), kw))
             uids.append(self.uid_count)
             self.uid_count += 1
@@ -777,6 +824,24 @@ class BatchGenerator:
                 buf[dst].copy_(buf[src])
             st.hist_len[dst:dst + 1].copy_(st.hist_len[src:src + 1])
 
+    # ------------------------------------------------------------------ per-row samplers (the lines of the row-table steps)
+    def _sampler_of(self, item) -> Sampler:
+        """the sampler of a queued request: its own, or the generator's"""
+        return item[3].get(_SAMPLER_KEY) or self.sampler
+
+    def _begin_row_sampling(self):
+        """From here on the steps draw every row with its own line.  Rows already running get the generator's sampler with a
+        fresh counter (written stream-ordered behind the step in flight, which still drew with the shared sampler)."""
+        self._row_sampling = True
+        lines = self._sampler_lines()
+        lines.zero_()
+        for r in range(len(self._rows)):
+            self._set_row_line(r, self.sampler, 0)
+
+    def _set_row_line(self, r: int, sampler: Sampler, count: int):
+        lines = self._sampler_lines()
+        lines[r].copy_(h2d(sampler.row_line(count), lines.device))
+
     # ------------------------------------------------------------------ token bitmasks of the mask rows (structured.py)
     def _finish_reason(self, row: _Row, tok: int, ahead: int = 0) -> Optional[str]:
         """the reference's finish rules (ar.py:1313-1316) for `tok` as token number row.num_tokens + ahead of its request"""
@@ -865,6 +930,9 @@ class BatchGenerator:
                 buf[dst:dst + 1].copy_(buf[src:src + 1])
             self._table[dst].copy_(self._table[src])
             self._move_row_penalties(dst, src)
+            if self._row_sampling:
+                lines = self._sampler_lines()
+                lines[dst].copy_(lines[src])
             self._rows[dst] = self._rows[src]
         del self._rows[live_after:]
         self._table[live_after:] = self._idle_row
@@ -879,6 +947,8 @@ class BatchGenerator:
             self._st.tok[n:].zero_()
             if getattr(self._st, "row_params", None) is not None:
                 self._st.row_params[n:].zero_()
+            if self._row_sampling:
+                self._sampler_lines()[n:].zero_()      # an idle row is a greedy row
         self._idle_steps = 0
 
     def _admit_begin(self):
@@ -952,6 +1022,8 @@ class BatchGenerator:
                 spec = b[3].get(_PROCS_KEY)
                 mproc = b[3].get(_MASKPROC_KEY)
                 self._set_row_penalties(r, p.pen, i, spec or mproc is not None)
+                if self._row_sampling:
+                    self._set_row_line(r, self._sampler_of(b), 1)      # (draw 0 was the first token, _prefill_requests)
                 py = b[3].get(_PYPROCS_KEY)
                 self._rows.append(_Row(uid=b[0], seq=seq, max_tokens=b[2], prompt_tokens=L, procs=spec, py_procs=py,
                                        tokens=h2d(np.asarray(b[1], dtype=np.int32).reshape(-1), lm.device) if py else None,
@@ -1062,12 +1134,14 @@ class BatchGenerator:
 
 def generate_batch_continuous(model, input_ids_list, pixel_values_list, grids, *, max_tokens=128, stop_ids=(),
                               sampler: Optional[Sampler] = None, batch_size: int = MAX_ROWS, use_graph: bool = True,
-                              extras: Optional[List[Optional[dict]]] = None, logits_processors=None, kv_bits=None):
+                              extras: Optional[List[Optional[dict]]] = None, logits_processors=None, kv_bits=None,
+                              samplers=None):
     """The reference's `_generate_batch` loop (ar.py:3212-3232) over the continuous generator: every request is queued
     at once, the generator keeps up to `batch_size` of them decoding and admits the next ones as rows free up.
     extras: per-request keyword arguments of the model's `get_input_embeddings` besides pixels / grid (phi3_v: image_sizes).
     logits_processors: one `make_logits_processors` spec (or None) per request, or ONE spec for all of them.
     kv_bits: 8 = every request's cache is a QuantizedKVCache from its first decode step on (BatchGenerator(kv_bits=8)).
+    samplers: one `make_sampler` spec (or None: `sampler`) per request - BatchGenerator.insert(..., samplers=).
     -> (tokens per request without the stop token, BatchStats)"""
     gen = BatchGenerator(model, None, max_tokens=max(max_tokens) if isinstance(max_tokens, (list, tuple)) else max_tokens,
                          stop_tokens=set(stop_ids), sampler=sampler,
@@ -1083,7 +1157,7 @@ def generate_batch_continuous(model, input_ids_list, pixel_values_list, grids, *
     if logits_processors is not None and not isinstance(logits_processors, (list, tuple)):
         logits_processors = [logits_processors] * len(input_ids_list)
     uids = gen.insert([np.asarray(i).reshape(-1) for i in input_ids_list], max_tokens, prompt_kwargs=kw,
-                      logits_processors=logits_processors)
+                      logits_processors=logits_processors, **({"samplers": samplers} if samplers is not None else {}))
     results = {u: [] for u in uids}
     tic = time.perf_counter()
     while gen.has_work:

@@ -333,8 +333,12 @@ static int decode_impl(Llm* m, const vlm_decode_args* a, void* stream, int* laun
   // VLM_DECODE_FUSED_TAIL: the step starts from h == embed[tok] and its sampler tail leaves the next step's h behind - the greedy
   // tail (vlm_sample_greedy_advance) or, with a temperature, the sampled one (vlm_sample_advance: final pick + advance + gather)
   const bool fused_flag = sample && (a->flags & VLM_DECODE_FUSED_TAIL);
-  const bool fused_tail = fused_flag && a->temperature == 0.f;
-  const bool fused_sampled = fused_flag && a->temperature > 0.f;
+  // VLM_DECODE_ROW_SAMPLER: the tail draws every row with its own line of sample_ws (the args' sampler scalars are not read)
+  const bool row_sampler = sample && (a->flags & VLM_DECODE_ROW_SAMPLER);
+  if ((a->flags & VLM_DECODE_ROW_SAMPLER) && (a->flags & VLM_DECODE_WINDOW)) return 1;
+  if (row_sampler && (!a->logprobs || !a->scratch || !a->sample_ws)) return 1;
+  const bool fused_tail = fused_flag && !row_sampler && a->temperature == 0.f;
+  const bool fused_sampled = fused_flag && !row_sampler && a->temperature > 0.f;
   if ((a->flags & VLM_DECODE_FUSED_TAIL) && !fused_flag) return 1;   // the flag promises h == embed[tok] at entry
   const Tuning& tn = m->tune;
   // VLM_DECODE_WINDOW (max_kv_size): ctx = [2][B] (n, w), pos = [2][B] (p, d).  The layer launches keep their signatures - the qkv
@@ -513,7 +517,13 @@ static int decode_impl(Llm* m, const vlm_decode_args* a, void* stream, int* laun
     n += (a->penalties->row_params && a->penalties->bias_stride > 0) ? 2 : 1;
   }
   if (sample) {
-    if (fused_tail) {
+    if (row_sampler) {
+      TRY(vlm_sample_rows_advance(a->logits, VL, B, c.vocab, a->logprobs, a->scratch, VL, a->tok, a->sample_ws,
+                                  fused_flag ? a->ctx : nullptr, a->pos, a->out_ring, a->ring_len, a->step, m->g.embed, a->h, D, D,
+                                  wn, stream));
+      n += vlm_sample_last_launches();
+      if (!fused_flag) { TRY(vlm_decode_advance_win(a->ctx, a->pos, a->tok, a->out_ring, a->ring_len, a->step, B, wn, stream)); ++n; }
+    } else if (fused_tail) {
       TRY(vlm_sample_greedy_advance_win(a->logits, VL, B, c.vocab, a->logprobs, VL, a->tok, a->sample_ws, a->ctx, a->pos,
                                         a->out_ring, a->ring_len, a->step, m->g.embed, a->h, D, D, wn, stream)); n += 2;
     } else if (fused_sampled) {

@@ -135,6 +135,12 @@ VLM_INTERNAL int vlm_sample_advance(const void* logits, int ld, int B, int V, vo
                                     void* ctx, void* pos, void* out_ring, int ring_len, void* step, const void* embed, void* h,
                                     int D, int ldh, VlmWindow wn, void* stream);
 
+/* sample.hip: the ROW-TABLE sampler (VLM_SAMPLE_ROW_TABLE: every row's own line in `workspace`) as the tail of the engine's step.
+ * ctx != NULL: the final pick also does vlm_decode_advance, the next step's embedding gather and every row's count += 1 (B <= 64,
+ * no window); ctx == NULL: the pick and the counts alone */
+VLM_INTERNAL int vlm_sample_rows_advance(const void* logits, int ld, int B, int V, void* logprobs, void* scratch, int ldlp, void* tok,
+                                         void* workspace, void* ctx, void* pos, void* out_ring, int ring_len, void* step,
+                                         const void* embed, void* h, int D, int ldh, VlmWindow wn, void* stream);
 
 /* gemm_bf16.hip: what the reduce launch of a split-K GEMM does ON TOP of its epilogue (the wide decode steps of engine.hip): the
  * launch the caller would otherwise issue next on the reduced rows.  Bit-identical to the two-launch sequence. */

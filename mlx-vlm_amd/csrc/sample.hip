@@ -32,10 +32,13 @@ constexpr int NBLK = 64;  // blocks per vocabulary row
 // re-armed between calls) of row b in the same words every time.  (Rounds 4-5 laid the arrays out [B][...] back to back: a
 // narrower step then found another step's Gumbel candidates where its histogram should be zero - ADVICE r05.)
 constexpr int CTL_WORDS = 128;
+constexpr int CTL_ROW_SAMPLER = 72;  // control words 72 .. 79 of a row's block: the row's sampler line of the row-table mode (RowLine below; all zero = greedy)
 constexpr int CTL_ROW_TICKET = 120;   // control word of a row's block: arrivals of the row's blocks in the fused greedy tail (zero between launches)
 constexpr int ROW_LSE = 0, ROW_CV = 2 * NBLK, ROW_CI = 3 * NBLK, ROW_HIST = 4 * NBLK, ROW_CTL = ROW_HIST + 65536;
 constexpr int ROW_W = ROW_CTL + CTL_WORDS;
 static_assert(ROW_HIST % 4 == 0 && ROW_W % 4 == 0, "the histogram of every row is cleared with 16-byte stores");
+static_assert(ROW_W == VLM_SAMPLE_ROW_STRIDE_WORDS && 64 + ROW_CTL + CTL_ROW_SAMPLER == VLM_SAMPLE_ROW_LINE_WORD && CTL_ROW_SAMPLER + 8 <= 80,
+              "the sampler line of row b is where include/vlm_hip.h tells callers to write it");
 
 // order-preserving map bf16 bits -> uint16 (ascending)
 __device__ __forceinline__ uint32_t bf_key(bf16_t b) { return (b & 0x8000u) ? (uint32_t)(~b & 0xffffu) : (uint32_t)(b | 0x8000u); }
@@ -149,8 +152,9 @@ __device__ __forceinline__ void gather_rows_256(const bf16_t* __restrict__ embed
   }
 }
 
-__global__ __launch_bounds__(256) void argmax_final_advance_kernel(const float* __restrict__ cand_v, const int* __restrict__ cand_i,
-                                                                   int* __restrict__ tok, int B, int V, SampleTail t) {
+// `lines` != nullptr (row-table mode): the control words of row 0 - every row's own draw counter advances with the step
+__device__ __forceinline__ void argmax_final_advance_body(const float* __restrict__ cand_v, const int* __restrict__ cand_i,
+                                                          int* __restrict__ tok, int B, int V, const SampleTail& t, uint32_t* lines) {
   __shared__ int s_tok[64];
   const int tid = threadIdx.x, li = tid & 63, wave = tid >> 6;
   for (int r = wave; r < B; r += 4) {
@@ -171,10 +175,71 @@ __global__ __launch_bounds__(256) void argmax_final_advance_kernel(const float* 
     tok[tid] = y;
     vlm_window_advance(t.ctx, t.pos, B, tid, t.wn);
     if (t.out_ring) vlm_ring_store(t.out_ring, (size_t)(st % t.ring_len) * B + tid, y, t.wn);
+    if (lines) lines[(size_t)tid * ROW_W + CTL_ROW_SAMPLER + 5] += 1u;
   }
   gather_rows_256(t.embed, t.h, s_tok, B, t.D, t.ldh, tid);
   __syncthreads();
   if (tid == 0) *t.step = st + 1;
+}
+
+__global__ __launch_bounds__(256) void argmax_final_advance_kernel(const float* __restrict__ cand_v, const int* __restrict__ cand_i,
+                                                                   int* __restrict__ tok, int B, int V, SampleTail t) {
+  argmax_final_advance_body(cand_v, cand_i, tok, B, V, t, nullptr);
+}
+
+// ------------------------------------------------------------------------------------------
+// Row-table mode (include/vlm_hip.h, vlm_sampler_params.input_is_logprobs bit 2 / VLM_DECODE_ROW_SAMPLER): every row draws with its
+// own sampler, read from eight control words of the row's workspace block that the host rewrites as requests come and go, so a
+// captured step keeps its launches and its arguments.  The kernels below are the scalar path's with the parameters fetched per row:
+// the same bodies, hence row b gives what the scalar call gives on that row alone at step = count_b.  The draw is keyed
+// (seed_b, count_b, 0, index): neither the row nor the neighbours enter.  A greedy row (temperature 0, what an all-zero line says)
+// passes through the same launches with every filter and the noise off: the argmax of its log-probs, lowest index on ties.
+// ------------------------------------------------------------------------------------------
+struct RowLine {
+  bool noise;           // temperature > 0: filters + Gumbel noise; otherwise the plain argmax
+  int use_top_p, use_min_p, top_k;
+  float thr_top_p, log_min_p, temp;
+  uint32_t seed, count;
+};
+// line = {temperature f32, top_p f32, min_p f32, top_k i32, seed u32, count u32, T(1 - top_p) f32, T(log(min_p)) f32}: the last two
+// are the scalar path's host conversions (sample_ex_impl), made where the host writes the line
+__device__ __forceinline__ RowLine load_row_line(const uint32_t* ctl_all, int b) {
+  const uint32_t* w = ctl_all + (size_t)b * ROW_W + CTL_ROW_SAMPLER;
+  RowLine r;
+  r.temp = __uint_as_float(w[0]);
+  r.noise = r.temp > 0.f;
+  const float top_p = __uint_as_float(w[1]), min_p = __uint_as_float(w[2]);
+  r.use_top_p = r.noise && top_p > 0.f && top_p < 1.f;
+  r.use_min_p = r.noise && min_p != 0.f;
+  r.top_k = r.noise ? (int)w[3] : 0;
+  r.seed = w[4];
+  r.count = w[5];
+  r.thr_top_p = __uint_as_float(w[6]);
+  r.log_min_p = r.use_min_p ? __uint_as_float(w[7]) : 0.f;
+  return r;
+}
+
+__global__ __launch_bounds__(64) void argmax_final_rows_kernel(const float* __restrict__ cand_v, const int* __restrict__ cand_i,
+                                                               int* __restrict__ tok, uint32_t* __restrict__ ctl_all) {
+  const int b = blockIdx.x;
+  float best = cand_v[(size_t)b * ROW_W + threadIdx.x];
+  int besti = cand_i[(size_t)b * ROW_W + threadIdx.x];
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float ov = __shfl_xor(best, o, 64);
+    const int oi = __shfl_xor(besti, o, 64);
+    if (ov > best || (ov == best && oi < besti)) { best = ov; besti = oi; }
+  }
+  if (threadIdx.x == 0) {
+    tok[b] = besti == 0x7fffffff ? 0 : besti;
+    ctl_all[(size_t)b * ROW_W + CTL_ROW_SAMPLER + 5] += 1u;      // the row's next draw
+  }
+}
+
+__global__ __launch_bounds__(256) void argmax_final_advance_rows_kernel(const float* __restrict__ cand_v, const int* __restrict__ cand_i,
+                                                                        int* __restrict__ tok, int B, int V, SampleTail t,
+                                                                        uint32_t* __restrict__ ctl_all) {
+  argmax_final_advance_body(cand_v, cand_i, tok, B, V, t, ctl_all);
 }
 
 
@@ -644,10 +709,11 @@ struct SamplerK {
 constexpr int XTC_MAX_SPECIAL = 256;
 constexpr int LH_WORDS = 32768 + 512;   // LDS histogram of the keys below 0x8000, one pad word per 64 keys
 
-__global__ __launch_bounds__(1024) void sample_filter_kernel(const bf16_t* __restrict__ lp_in, int ld_in,
-                                                             bf16_t* __restrict__ lp_all, int ldlp, int V,
-                                                             uint32_t* __restrict__ hist_all,
-                                                             const SamplerK p, const int* __restrict__ step_ptr) {
+// (the body of sample_filter_kernel and of its row-table form: `step` = the draw counter of the call / of the row)
+__device__ __forceinline__ void sample_filter_body(const bf16_t* __restrict__ lp_in, int ld_in,
+                                                   bf16_t* __restrict__ lp_all, int ldlp, int V,
+                                                   uint32_t* __restrict__ hist_all,
+                                                   const SamplerK& p, const uint32_t step) {
   __shared__ float red[32];
   __shared__ uint32_t s_thr_key, s_thr_keep;
   __shared__ unsigned long long s_best;
@@ -660,7 +726,6 @@ __global__ __launch_bounds__(1024) void sample_filter_kernel(const bf16_t* __res
   const int b = blockIdx.x, tid = threadIdx.x;
   bf16_t* lp = lp_all + (size_t)b * ldlp;           // scratch copy that the filters mask in place
   uint32_t* hist = hist_all + (size_t)b * ROW_W;
-  const uint32_t step = (uint32_t)(step_ptr ? *step_ptr : 0);
 #ifdef VLM_SAMPLE_STAMPS
   // probe build (scripts/sampler_stamps.py): phase stamps of the 100 MHz wall clock in the words of the global histogram that
   // the LDS half has made free
@@ -1041,6 +1106,27 @@ __global__ __launch_bounds__(1024) void sample_filter_kernel(const bf16_t* __res
 #endif
 }
 
+__global__ __launch_bounds__(1024) void sample_filter_kernel(const bf16_t* __restrict__ lp_in, int ld_in,
+                                                             bf16_t* __restrict__ lp_all, int ldlp, int V,
+                                                             uint32_t* __restrict__ hist_all,
+                                                             const SamplerK p, const int* __restrict__ step_ptr) {
+  sample_filter_body(lp_in, ld_in, lp_all, ldlp, V, hist_all, p, (uint32_t)(step_ptr ? *step_ptr : 0));
+}
+
+// row-table form: the row's own top-p / min-p / top-k (none on a greedy or unfiltered row: the launch then only copies the row to
+// `lp_all`, where the draw of every row reads)
+__global__ __launch_bounds__(1024) void sample_filter_rows_kernel(const bf16_t* __restrict__ lp_in, int ld_in,
+                                                                  bf16_t* __restrict__ lp_all, int ldlp, int V,
+                                                                  uint32_t* __restrict__ hist_all, const uint32_t* __restrict__ ctl_all) {
+  const RowLine r = load_row_line(ctl_all, blockIdx.x);
+  SamplerK p{};
+  p.use_top_p = r.use_top_p; p.thr_top_p = r.thr_top_p;
+  p.use_min_p = r.use_min_p; p.min_keep = 1; p.log_min_p = r.log_min_p;
+  p.top_k = r.top_k;
+  p.temp = r.temp; p.seed = r.seed;
+  sample_filter_body(lp_in, ld_in, lp_all, ldlp, V, hist_all, p, r.count);
+}
+
 // ------------------------------------------------------------------------------------------
 // top-p (round 5) and, since round 6, any subset of top-p / min-p / top-k (make_sampler's common chain), a row split over SPLIT_G
 // workgroups.  The
@@ -1156,8 +1242,8 @@ __global__ __launch_bounds__(256) void topp_hist_kernel(const bf16_t* __restrict
 // key whose value reaches T(max + T(log min_p)) (sample_utils.py:266-286); top-k = a descending count over the surviving bins
 // (sample_utils.py:169-175: ties at the k-th value keep the LOWEST indices of what is left of that bin) - and ctl carries the final
 // (key, [lo, hi)) for the count / mask launches.  Same survivors, bit for bit, as sample_filter_kernel's three passes over the row.
-__global__ __launch_bounds__(1024) void topp_cross_kernel(const uint32_t* __restrict__ hist_all, uint32_t* __restrict__ ctl_all,
-                                                          float thr, int use_top_p, int use_min_p, float log_min_p, int top_k, int V) {
+__device__ __forceinline__ void topp_cross_body(const uint32_t* __restrict__ hist_all, uint32_t* __restrict__ ctl_all,
+                                                float thr, int use_top_p, int use_min_p, float log_min_p, int top_k, int V) {
   __shared__ float scan_f[17];
   __shared__ uint32_t scan_u2[17];
   __shared__ uint32_t s_kmax, s_k2, s_keep2;
@@ -1358,6 +1444,17 @@ __global__ __launch_bounds__(1024) void topp_cross_kernel(const uint32_t* __rest
   }
 }
 
+__global__ __launch_bounds__(1024) void topp_cross_kernel(const uint32_t* __restrict__ hist_all, uint32_t* __restrict__ ctl_all,
+                                                          float thr, int use_top_p, int use_min_p, float log_min_p, int top_k, int V) {
+  topp_cross_body(hist_all, ctl_all, thr, use_top_p, use_min_p, log_min_p, top_k, V);
+}
+
+// row-table form: the chain of the row's own line (no filter on: key 0 with its whole bin - nothing is removed, nothing ranked)
+__global__ __launch_bounds__(1024) void topp_cross_rows_kernel(const uint32_t* __restrict__ hist_all, uint32_t* __restrict__ ctl_all, int V) {
+  const RowLine r = load_row_line(ctl_all, blockIdx.x);
+  topp_cross_body(hist_all, ctl_all, r.thr_top_p, r.use_top_p, r.use_min_p, r.log_min_p, r.top_k, V);
+}
+
 __device__ __forceinline__ uint32_t hits8(const u32x4_t& w, uint32_t tb) {
   const uint32_t w0 = w[0], w1 = w[1], w2 = w[2], w3 = w[3];
   return (uint32_t)((w0 & 0xffffu) == tb) | (uint32_t)((w0 >> 16) == tb) << 1 | (uint32_t)((w1 & 0xffffu) == tb) << 2 |
@@ -1389,15 +1486,15 @@ __global__ __launch_bounds__(256) void topp_count_kernel(const bf16_t* __restric
 // ... and the draw: z_i = x_i / temp - log(-log(u_i)) over the survivors as they are written (gumbel_partial_kernel's arithmetic,
 // its index-keyed RNG and its lowest-index tie rule; the best (z, i) of the slice lands where that kernel's block would leave
 // it), so the filtered row is not read back by a launch of its own.
-__global__ __launch_bounds__(256) void topp_mask_kernel(const bf16_t* __restrict__ lp_in, int ld_in, bf16_t* __restrict__ out_all,
-                                                        int ldo, int V, uint32_t* __restrict__ hist_all, uint32_t* __restrict__ ctl_all,
-                                                        float temp, uint32_t seed, const int* __restrict__ step_ptr,
-                                                        float* __restrict__ cand_v, int* __restrict__ cand_i) {
+// (the draw is keyed (seed, step, hrow, index); noise false - a greedy row of the row-table form - z is the log-prob itself)
+__device__ __forceinline__ void topp_mask_body(const bf16_t* __restrict__ lp_in, int ld_in, bf16_t* __restrict__ out_all,
+                                               int ldo, int V, uint32_t* __restrict__ hist_all, uint32_t* __restrict__ ctl_all,
+                                               float temp, uint32_t seed, const uint32_t step, const uint32_t hrow, const bool noise,
+                                               float* __restrict__ cand_v, int* __restrict__ cand_i) {
   __shared__ uint32_t wcnt[4];
   __shared__ float sv[4];
   __shared__ int si[4];
-  const uint32_t step = (uint32_t)(step_ptr ? *step_ptr : 0);
-  const float it = 1.0f / temp;
+  const float it = noise ? 1.0f / temp : 0.f;
   float best = -INFINITY;
   int besti = 0x7fffffff;
   const int s = blockIdx.x, b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -1466,8 +1563,8 @@ __global__ __launch_bounds__(256) void topp_mask_kernel(const bf16_t* __restrict
         const bf16_t xb = (bf16_t)((e & 1) ? (wv[e >> 1] >> 16) : (wv[e >> 1] & 0xffffu));
         if (xb == NEG_INF_BF) continue;                     // (a removed token cannot win: -inf + gumbel = -inf)
         const int i = c * 8 + e;
-        const float zg = __builtin_fmaf(bf2f(xb), it, -logf(-logf(hash_uniform(seed, step, (uint32_t)b, (uint32_t)i))));      // (one fma,
-                                                                                  // as hipcc contracts gumbel_partial_kernel's x * it + g)
+        const float zg = noise ? __builtin_fmaf(bf2f(xb), it, -logf(-logf(hash_uniform(seed, step, hrow, (uint32_t)i))))      // (one fma,
+                               : bf2f(xb);                                        // as hipcc contracts gumbel_partial_kernel's x * it + g)
         if (zg > best || (zg == best && i < besti)) { best = zg; besti = i; }
       }
     }
@@ -1493,28 +1590,42 @@ __global__ __launch_bounds__(256) void topp_mask_kernel(const bf16_t* __restrict
   if (s == 0 && tid == 0) { ctl[3] = 0u; ctl[4] = 0xffffffffu; ctl[5] = 0u; }
 }
 
+__global__ __launch_bounds__(256) void topp_mask_kernel(const bf16_t* __restrict__ lp_in, int ld_in, bf16_t* __restrict__ out_all,
+                                                        int ldo, int V, uint32_t* __restrict__ hist_all, uint32_t* __restrict__ ctl_all,
+                                                        float temp, uint32_t seed, const int* __restrict__ step_ptr,
+                                                        float* __restrict__ cand_v, int* __restrict__ cand_i) {
+  topp_mask_body(lp_in, ld_in, out_all, ldo, V, hist_all, ctl_all, temp, seed, (uint32_t)(step_ptr ? *step_ptr : 0), (uint32_t)blockIdx.y,
+                 true, cand_v, cand_i);
+}
+
+__global__ __launch_bounds__(256) void topp_mask_rows_kernel(const bf16_t* __restrict__ lp_in, int ld_in, bf16_t* __restrict__ out_all,
+                                                             int ldo, int V, uint32_t* __restrict__ hist_all, uint32_t* __restrict__ ctl_all,
+                                                             float* __restrict__ cand_v, int* __restrict__ cand_i) {
+  const RowLine r = load_row_line(ctl_all, blockIdx.y);
+  topp_mask_body(lp_in, ld_in, out_all, ldo, V, hist_all, ctl_all, r.temp, r.seed, r.count, 0u, r.noise, cand_v, cand_i);
+}
+
 // categorical(logprobs / temp) (sample_utils.py:385-387) by Gumbel-max with the counter hash RNG over the (filtered) row:
 // z_i = x_i / temp - log(-log(u_i)), u_i = hash(seed, step, row, i); the token is argmax z (lowest index on a tie).  NBLK
 // workgroups per row leave their best (z, i) where the greedy path leaves its candidates and argmax_final_kernel picks the
 // winner.  (Inside the one-workgroup-per-row filter kernel this pass was 45-52 us of hash + two logs per element on ONE CU.)
-__global__ __launch_bounds__(256) void gumbel_partial_kernel(const bf16_t* __restrict__ lp_all, int ldlp, int V, float temp,
-                                                             uint32_t seed, const int* __restrict__ step_ptr,
-                                                             float* __restrict__ cand_v, int* __restrict__ cand_i) {
+__device__ __forceinline__ void gumbel_partial_body(const bf16_t* __restrict__ lp_all, int ldlp, int V, float temp,
+                                                    uint32_t seed, const uint32_t step, const uint32_t hrow, const bool noise,
+                                                    float* __restrict__ cand_v, int* __restrict__ cand_i) {
   __shared__ float sv[4];
   __shared__ int si[4];
   const int b = blockIdx.y, blk = blockIdx.x, tid = threadIdx.x;
-  const uint32_t step = (uint32_t)(step_ptr ? *step_ptr : 0);
   const int per = ((V + NBLK - 1) / NBLK + 7) & ~7;
   const int lo = blk * per, hi = min(V, lo + per);
   const bf16_t* row = lp_all + (size_t)b * ldlp;
-  const float it = 1.0f / temp;
+  const float it = noise ? 1.0f / temp : 0.f;
   float best = -INFINITY;
   int besti = 0x7fffffff;
   for (int i = lo + tid; i < hi; i += 256) {
     const bf16_t xb = row[i];
     if (xb == NEG_INF_BF) continue;                     // (a removed token cannot win: -inf + gumbel = -inf)
-    const float u = hash_uniform(seed, step, (uint32_t)b, (uint32_t)i);
-    const float z = __builtin_fmaf(bf2f(xb), it, -logf(-logf(u)));      // x / temp + g as ONE fma (what hipcc's contraction made of the
+    const float u = hash_uniform(seed, step, hrow, (uint32_t)i);
+    const float z = noise ? __builtin_fmaf(bf2f(xb), it, -logf(-logf(u))) : bf2f(xb);      // x / temp + g as ONE fma (what hipcc's contraction made of the
                                                                         // two statements before; written out so that topp_mask_kernel's copy
                                                                         // of the draw cannot drift from it)
     if (z > best || (z == best && i < besti)) { best = z; besti = i; }
@@ -1533,6 +1644,19 @@ __global__ __launch_bounds__(256) void gumbel_partial_kernel(const bf16_t* __res
     cand_v[(size_t)b * ROW_W + blk] = best;
     cand_i[(size_t)b * ROW_W + blk] = besti;
   }
+}
+
+__global__ __launch_bounds__(256) void gumbel_partial_kernel(const bf16_t* __restrict__ lp_all, int ldlp, int V, float temp,
+                                                             uint32_t seed, const int* __restrict__ step_ptr,
+                                                             float* __restrict__ cand_v, int* __restrict__ cand_i) {
+  gumbel_partial_body(lp_all, ldlp, V, temp, seed, (uint32_t)(step_ptr ? *step_ptr : 0), (uint32_t)blockIdx.y, true, cand_v, cand_i);
+}
+
+__global__ __launch_bounds__(256) void gumbel_partial_rows_kernel(const bf16_t* __restrict__ lp_all, int ldlp, int V,
+                                                                  const uint32_t* __restrict__ ctl_all,
+                                                                  float* __restrict__ cand_v, int* __restrict__ cand_i) {
+  const RowLine r = load_row_line(ctl_all, blockIdx.y);
+  gumbel_partial_body(lp_all, ldlp, V, r.temp, r.seed, r.count, 0u, r.noise, cand_v, cand_i);
 }
 
 // float32 -> bf16 value, round to nearest even (host side of the weak-typed scalars)
@@ -1693,11 +1817,99 @@ static int sample_ex_impl(const void* logits, int ld, int B, int V, void* logpro
   return VLM_OK;
 }
 
+// Row-table mode: every row's sampler comes from its line in the workspace (RowLine above).  The launch sequence is a function of
+// (B, V, leading dimensions, alignment) alone - the split chain where its shape conditions hold, the one-workgroup filter and the
+// Gumbel partials otherwise - and every row, greedy ones included, passes through all of it: a captured call can be replayed
+// over any table.  The last launch advances every row's draw counter (and, with `tail`, does the step's bookkeeping).
+static int sample_rows_impl(const void* logits, int ld, int B, int V, void* logprobs, void* scratch, int ldlp, void* tok,
+                            void* workspace, bool lp_given, void* stream, const SampleTail* tail) {
+  if (!logits || !tok || !workspace || !scratch || (!logprobs && !lp_given) || B <= 0 || V <= 0) return VLM_ERR_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  t_last_launches = 0;
+  float* ws = (float*)((char*)workspace + 256);
+  float* cand_v = ws + ROW_CV;
+  int* cand_i = (int*)(ws + ROW_CI);
+  uint32_t* hist = (uint32_t*)(ws + ROW_HIST);
+  uint32_t* ctl = (uint32_t*)(ws + ROW_CTL);
+  static const bool split_env = [] { const char* e = getenv("VLM_SAMPLE_SPLIT"); return !e || atoi(e) != 0; }();   // A/B knob of the scalar path
+  const bool split = split_env && V % 8 == 0 && V >= 8192 && (lp_given ? ld : ldlp) % 8 == 0 && ldlp % 8 == 0 &&
+                     ((uintptr_t)(lp_given ? logits : logprobs) & 15) == 0 && ((uintptr_t)scratch & 15) == 0;
+  const bool fused_lp = split && !lp_given && ld % 8 == 0 && ((uintptr_t)logits & 15) == 0;
+  constexpr int LDS = LH_WORDS * (int)sizeof(uint32_t);
+  if (!lp_given) {
+    hipLaunchKernelGGL(lse_partial_kernel, dim3(NBLK, B), dim3(256), 0, st, (const bf16_t*)logits, ld, V, ws);
+    VLM_CHECK_LAUNCH(); ++t_last_launches;
+    if (!fused_lp) {
+      hipLaunchKernelGGL(logprob_argmax_kernel, dim3(NBLK, B), dim3(256), 0, st, (const bf16_t*)logits, ld, V, ws,
+                         (bf16_t*)logprobs, ldlp, cand_v, cand_i);
+      VLM_CHECK_LAUNCH(); ++t_last_launches;
+    }
+  }
+  const bf16_t* row_in = lp_given ? (const bf16_t*)logits : (const bf16_t*)logprobs;
+  const int ld_in = lp_given ? ld : ldlp;
+  if (split) {
+    static const hipError_t attr_a = hipFuncSetAttribute(reinterpret_cast<const void*>(&topp_hist_kernel<false>),
+                                                         hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
+    static const hipError_t attr_a2 = hipFuncSetAttribute(reinterpret_cast<const void*>(&topp_hist_kernel<true>),
+                                                          hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
+    constexpr int LDS_B = LDS + PW_MAX * (int)sizeof(float);
+    static const hipError_t attr_b = hipFuncSetAttribute(reinterpret_cast<const void*>(&topp_cross_rows_kernel),
+                                                         hipFuncAttributeMaxDynamicSharedMemorySize, LDS_B);
+    for (hipError_t e : {attr_a, attr_a2, attr_b})
+      if (e != hipSuccess) return VLM_ERR_HIP + (int)e;
+    if (fused_lp)
+      hipLaunchKernelGGL(topp_hist_kernel<true>, dim3(SPLIT_G, B), dim3(256), LDS, st, (const bf16_t*)logits, ld, V, hist, ctl,
+                         (const float*)ws, (bf16_t*)logprobs, ldlp);
+    else
+      hipLaunchKernelGGL(topp_hist_kernel<false>, dim3(SPLIT_G, B), dim3(256), LDS, st, row_in, ld_in, V, hist, ctl,
+                         (const float*)nullptr, (bf16_t*)nullptr, 0);
+    VLM_CHECK_LAUNCH(); ++t_last_launches;
+    hipLaunchKernelGGL(topp_cross_rows_kernel, dim3(B), dim3(1024), LDS_B, st, (const uint32_t*)hist, ctl, V);
+    VLM_CHECK_LAUNCH(); ++t_last_launches;
+    hipLaunchKernelGGL(topp_count_kernel, dim3(SPLIT_G, B), dim3(256), 0, st, row_in, ld_in, V, ctl);
+    VLM_CHECK_LAUNCH(); ++t_last_launches;
+    hipLaunchKernelGGL(topp_mask_rows_kernel, dim3(SPLIT_G, B), dim3(256), 0, st, row_in, ld_in, (bf16_t*)scratch, ldlp, V, hist, ctl,
+                       cand_v, cand_i);
+    VLM_CHECK_LAUNCH(); ++t_last_launches;
+  } else {
+    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&sample_filter_rows_kernel),
+                                                       hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
+    if (attr != hipSuccess) return VLM_ERR_HIP + (int)attr;
+    hipLaunchKernelGGL(sample_filter_rows_kernel, dim3(B), dim3(1024), LDS, st, row_in, ld_in, (bf16_t*)scratch, ldlp, V, hist,
+                       (const uint32_t*)ctl);
+    VLM_CHECK_LAUNCH(); ++t_last_launches;
+    hipLaunchKernelGGL(gumbel_partial_rows_kernel, dim3(NBLK, B), dim3(256), 0, st, (const bf16_t*)scratch, ldlp, V,
+                       (const uint32_t*)ctl, cand_v, cand_i);
+    VLM_CHECK_LAUNCH(); ++t_last_launches;
+  }
+  if (tail) hipLaunchKernelGGL(argmax_final_advance_rows_kernel, dim3(1), dim3(256), 0, st, cand_v, cand_i, (int*)tok, B, V, *tail, ctl);
+  else hipLaunchKernelGGL(argmax_final_rows_kernel, dim3(B), dim3(64), 0, st, cand_v, cand_i, (int*)tok, ctl);
+  VLM_CHECK_LAUNCH(); ++t_last_launches;
+  return VLM_OK;
+}
+
 extern "C" int vlm_sample_ex(const void* logits, int ld, int B, int V, void* logprobs, void* scratch, int ldlp, void* tok,
                              void* workspace, const vlm_sampler_params* sp, const void* step_ptr, void* stream) {
   // input_is_logprobs == 2 (added within ABI v8): not a sampler call - the top_k best log-probs of every row, csrc/top_logprobs.hip
   if (sp && sp->input_is_logprobs == 2) return vlm_top_logprobs(logits, ld, B, V, sp->top_k, tok, logprobs, stream);
+  // bit 2 (VLM_SAMPLE_ROW_TABLE, added within ABI v8): the rows' own samplers, from their lines in the workspace
+  if (sp && (sp->input_is_logprobs & VLM_SAMPLE_ROW_TABLE)) {
+    if (sp->input_is_logprobs & ~(VLM_SAMPLE_ROW_TABLE | 1)) return VLM_ERR_ARG;
+    if (sp->xtc_probability > 0.0 || (sp->typical_p > 0.0 && sp->typical_p < 1.0) || sp->top_n_sigma > 0.0 || sp->p_less) return VLM_ERR_ARG;
+    return sample_rows_impl(logits, ld, B, V, logprobs, scratch, ldlp, tok, workspace, (sp->input_is_logprobs & 1) != 0, stream, nullptr);
+  }
   return sample_ex_impl(logits, ld, B, V, logprobs, scratch, ldlp, tok, workspace, sp, step_ptr, stream, nullptr);
+}
+
+// the row-table sampler as the tail of the engine's step (VLM_DECODE_ROW_SAMPLER); ctx == NULL: the pick alone, as vlm_sample_ex
+VLM_INTERNAL int vlm_sample_rows_advance(const void* logits, int ld, int B, int V, void* logprobs, void* scratch, int ldlp, void* tok,
+                                         void* workspace, void* ctx, void* pos, void* out_ring, int ring_len, void* step,
+                                         const void* embed, void* h, int D, int ldh, VlmWindow wn, void* stream) {
+  if (!ctx) return sample_rows_impl(logits, ld, B, V, logprobs, scratch, ldlp, tok, workspace, false, stream, nullptr);
+  if (!pos || !step || !embed || !h || wn.M > 0) return VLM_ERR_ARG;
+  if (B > 64 || D % 8 || ldh % 8 || (out_ring && ring_len <= 0)) return VLM_ERR_SHAPE;
+  const SampleTail t{(int*)ctx, (int*)pos, (int*)out_ring, (int*)step, ring_len, (const bf16_t*)embed, (bf16_t*)h, D, ldh, wn};
+  return sample_rows_impl(logits, ld, B, V, logprobs, scratch, ldlp, tok, workspace, false, stream, &t);
 }
 
 // vlm_sample (temperature > 0) + vlm_decode_advance + the next step's vlm_embed_gather, for the engine's captured step (internal.h)

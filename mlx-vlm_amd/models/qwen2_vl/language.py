@@ -980,11 +980,14 @@ class LanguageModel:
         return bool(flags) and flags.pop()
 
     def decode_step_rows(self, st: DecodeState, B: int, block_table: torch.Tensor, sampler_args: dict,
-                         use_graph: bool = True, with_logprobs: bool = True, row_penalties: bool = False, q8: bool = False):
+                         use_graph: bool = True, with_logprobs: bool = True, row_penalties: bool = False, q8: bool = False,
+                         row_sampler: bool = False):
         """One decode step over rows 0..B-1 of `st` (B in {1, 2, 4, 8}), addressing the KV pool through the caller's own
         `block_table` (int32 [>= B, max_pages]).  A continuous batch keeps such a table so that a sequence changes
         batch row by copying one table row - no KV bytes move (the reference's `filter`/`extend` copy the caches,
-        cache.py:1100-1201).  Graphs are cached per (B, nsplit, table, sampler) inside the engine."""
+        cache.py:1100-1201).  Graphs are cached per (B, nsplit, table, sampler) inside the engine.
+        row_sampler: the tail draws every row with its own line of st.sample_ws (ops.sample_row_table; _lib.DECODE_ROW_SAMPLER) -
+        `sampler_args` are then not read by the step."""
         L = _lib.lib()
         stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
         pool = self.pool
@@ -995,9 +998,13 @@ class LanguageModel:
                          pool.max_pages, *q, 1 if q8 else 0)
         check(L.vlm_llm_set_kv(self._handle, C.byref(kv)), "llm_set_kv")
         # row_penalties: the step applies every row's own logits processors (device tables of the state) before sampling
-        args = st.args(B=B, with_logprobs=with_logprobs, penalties="rows" if row_penalties else None, **sampler_args)
+        if row_sampler:
+            args = st.args(B=B, with_logprobs=True, penalties="rows" if row_penalties else None, flags=_lib.DECODE_ROW_SAMPLER)
+        else:
+            args = st.args(B=B, with_logprobs=with_logprobs, penalties="rows" if row_penalties else None, **sampler_args)
         if use_graph:
-            key = ("rows", B, st.nsplit, block_table.data_ptr(), with_logprobs, bool(row_penalties), bool(q8), tuple(sorted(sampler_args.items())))
+            key = ("rows", B, st.nsplit, block_table.data_ptr(), with_logprobs, bool(row_penalties), bool(q8),
+                   "row_sampler" if row_sampler else tuple(sorted(sampler_args.items())))
             if st.graph_key != key or getattr(self, "_graph_owner", None) is not st:
                 check(L.vlm_llm_decode_graph_build(self._handle, C.byref(args), stream), "decode_graph_build")
                 st.graph_key = key

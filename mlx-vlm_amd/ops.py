@@ -551,6 +551,51 @@ def sample(logits, temperature=0.0, top_p=1.0, min_p=0.0, top_k=0, seed=0, step=
     return tok, lp
 
 
+def sample_row_table(ws):
+    """The row-table lines of a sampler workspace: an int32 [B, 8] VIEW - row b is the eight control words of row b's block
+    that vlm_sample_ex reads in row-table mode (include/vlm_hip.h VLM_SAMPLE_ROW_TABLE; sample_utils.Sampler.row_line builds
+    one).  Writing the view rewrites the samplers of the next call or graph replay; all zero = every row greedy."""
+    words = ws.view(torch.int32)
+    B = (words.numel() - 64) // _lib.SAMPLE_ROW_STRIDE_WORDS
+    return words.as_strided((B, 8), (_lib.SAMPLE_ROW_STRIDE_WORDS, 1), words.storage_offset() + _lib.SAMPLE_ROW_LINE_WORD)
+
+
+def sample_rows(logits, table=None, want_logprobs=True, ws=None, return_filtered=False, input_is_logprobs=False):
+    """Every row drawn with its OWN sampler (vlm_sample_ex in row-table mode) -> (tokens int32 [B], logprobs bf16 [B, V] or
+    None[, filtered rows bf16 [B, V] when return_filtered]).  table: int32 [B, 8] tensor, one sample_utils.Sampler.row_line
+    per row - copied into the lines of `ws` before the call, and updated in place afterwards (the call advances every row's
+    count by one); None: the lines already in `ws` (sample_row_table) are used and advanced where they are.  Row b is the
+    scalar ops.sample on that row alone with the line's scalars and step = count, except that the draw's key leaves the row
+    index out: (seed, count, 0, index).  input_is_logprobs: `logits` already holds log-probs, for every row."""
+    _dev(logits)
+    B, V = logits.shape
+    if ws is None:
+        if table is None:
+            raise ValueError("sample_rows: a table, or a workspace that holds the rows' lines")
+        ws = sample_workspace(B, logits.device)
+    lines = sample_row_table(ws)
+    if lines.shape[0] < B:
+        raise ValueError(f"sample_rows: the workspace holds {lines.shape[0]} rows, the call has {B}")
+    if table is not None:
+        if not isinstance(table, torch.Tensor) or table.dtype != torch.int32 or tuple(table.shape) != (B, 8):
+            raise ValueError(f"sample_rows: table is an int32 [{B}, 8] tensor (sample_utils.Sampler.row_line per row)")
+        lines[:B].copy_(table)
+    lp_given = bool(input_is_logprobs)
+    tok = torch.empty(B, dtype=torch.int32, device=logits.device)
+    lp = None if lp_given else torch.empty(B, V, dtype=torch.bfloat16, device=logits.device)
+    scratch = torch.empty(B, V, dtype=torch.bfloat16, device=logits.device)
+    sp = _lib.SamplerParams(input_is_logprobs=_lib.SAMPLE_MODE_ROW_TABLE | int(lp_given), typical_p=1.0, min_tokens_to_keep=1)
+    check(_lib.lib().vlm_sample_ex(_p(logits), logits.stride(0), B, V, _p(lp), _p(scratch), V, _p(tok), _p(ws), sp, None,
+                                   _stream()), "sample_rows")
+    if table is not None:
+        table.copy_(lines[:B])
+    if lp_given:
+        lp = logits
+    elif not want_logprobs:
+        lp = None
+    return (tok, lp, scratch) if return_filtered else (tok, lp)
+
+
 def top_logprobs(logprobs, k, ws=None, out=None):
     """The k best entries of every row of bf16 log-probs [B, V] (any row stride >= V) as the reference's batch generator lists
     them (ar.py:1092-1122: argsort ascending, the last k, reversed): value descending, the HIGHER index first among equal

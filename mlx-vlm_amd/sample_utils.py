@@ -50,6 +50,38 @@ class Sampler:
         return dict(temperature=float(self.temp), top_p=float(self.top_p if 0 < self.top_p < 1 else 1.0),
                     min_p=float(self.min_p), top_k=int(self.top_k), seed=int(self.seed))
 
+    def row_line(self, count: int = 0):
+        """This sampler as one line of the row-table mode (ops.sample_rows, include/vlm_hip.h VLM_SAMPLE_ROW_TABLE): int32 [8]
+        holding the bits of {temperature f32, top_p f32, min_p f32, top_k i32, seed u32, count u32, T(1 - top_p) f32,
+        T(log(min_p)) f32}.  The first five are `engine_args()` narrowed to 32 bits; the last two are the conversions the scalar
+        call makes on its side of the C ABI, made here instead: the double, to float32, rounded to bf16 (nearest even).  A
+        greedy sampler is the all-zero line (plus its count).  Only top-p / min-p / top-k travel in a line."""
+        import math
+
+        import numpy as np
+
+        if self.extended:
+            raise NotImplementedError("a row-table line carries top_p, min_p (min_tokens_to_keep = 1) and top_k only")
+        line = np.zeros(8, dtype=np.uint32)
+        line[5] = int(count) & 0xFFFFFFFF
+        if self.greedy:
+            return line.view(np.int32)
+        a = self.engine_args()
+
+        def rbf(x: float) -> np.float32:
+            u = int(np.float32(x).view(np.uint32))
+            if (u & 0x7FFFFFFF) <= 0x7F800000:
+                u = ((u + 0x7FFF + ((u >> 16) & 1)) & 0xFFFF0000) & 0xFFFFFFFF
+            return np.uint32(u).view(np.float32)
+
+        f = line.view(np.float32)
+        f[0], f[1], f[2] = a["temperature"], a["top_p"], a["min_p"]
+        line[3] = np.int32(a["top_k"]).view(np.uint32)
+        line[4] = a["seed"] & 0xFFFFFFFF
+        f[6] = rbf(1.0 - a["top_p"])
+        f[7] = rbf(math.log(a["min_p"])) if a["min_p"] != 0 else 0.0
+        return line.view(np.int32)
+
     def sample_args(self) -> dict:
         """keyword arguments of ops.sample (vlm_sample_ex) - python floats, converted on the other side of the C ABI"""
         return dict(self.engine_args(), top_p=float(self.top_p), min_tokens_to_keep=int(self.min_tokens_to_keep),
