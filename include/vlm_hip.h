@@ -89,7 +89,12 @@ int vlm_gemm_set_staging(int mode);
 
 /* y[M,N] = epi(x[M,K] . W[N,K]^T) for the decode step, M in {1,2,4,8}; weight streaming.
  * norm_w != NULL fuses y = f(RMSNorm(x; norm_w, eps)) (language.py:130-133,149-153,200).
- * Same reference call sites as vlm_gemm_bf16 at L == 1. */
+ * Same reference call sites as vlm_gemm_bf16 at L == 1.
+ * Shapes: K % 8 == 0.  With norm_w: K <= 4096 and M * K * 2 <= 64 KiB of staged rows.  Without: K <= 3584 on the same
+ * kernel, longer rows on the split-K kernel: NONE / BIAS / RESIDUAL up to K <= 20480 (<= 30720 for up to 4 rows - the 72B down
+ * projection); SWIGLU, whose gate / up pairs need two weight rows per workgroup, up to K <= 20480 for 1 or 2 rows and
+ * K <= 10240 for 4 or 8.  Anything else returns 2 and enqueues nothing.  A hidden size past 4096 (up to
+ * 8192, Qwen2-VL-72B) runs vlm_rmsnorm_residual and then this call without norm_w: measured faster than a fused kernel. */
 int vlm_gemv_bf16(const void* x, const void* W, const void* bias, const void* res, const void* norm_w, void* y, int M,
                   int N, int K, int ldx, int ldw, int ldy, int ldres, float eps, int epilogue, void* stream);
 
@@ -101,6 +106,8 @@ int vlm_gemv_bf16(const void* x, const void* W, const void* bias, const void* re
  *   layout: row m owns pages [m * max_pages, (m + 1) * max_pages) of the pools as passed (no table load).
  * vlm_gemv_attn_out: h += merge(attention split partials) Wo^T (language.py:115-120,151): the split-K merge of
  *   vlm_attn_decode_paged is the GEMV prologue, the residual add its epilogue. */
+/* hidden <= 4096, hidden % 8 == 0, D % 16 == 0, M in {1,2,4,8} with M * hidden * 2 <= 64 KiB (else 2, nothing enqueued: a wider
+ * model runs vlm_rmsnorm_residual, vlm_gemv_bf16 with VLM_EPI_BIAS and the rotary + KV-write launch - the engine does) */
 int vlm_gemv_qkv_rope_kvwrite(const void* h, const void* norm_w, float eps, const void* Wqkv, const void* bqkv,
                               void* qkv, int ldq, int M, int hidden, int Hq, int Hkv, int D, const void* pos,
                               const void* slot, const void* inv_freq, const void* block_table, int max_pages,
@@ -111,7 +118,10 @@ int vlm_gemv_qkv_rope_kvwrite(const void* h, const void* norm_w, float eps, cons
  * products per weight chunk.  `workspace` (vlm_gemv_workspace_bytes() bytes, ZERO-INITIALISED once, owned by the caller;
  * launches sharing it must be ordered by one stream) lets projections with few output rows and a long K (o_proj, down)
  * split K over workgroups: fp32 partial tiles + an arrival ticket per tile, summed in a fixed order (deterministic).
- * NULL = no split; shapes that then do not fit fall back to the kernels of vlm_gemv_bf16 (M in {1, 2, 4, 8}). */
+ * NULL = no split; shapes that then do not fit fall back to the kernels of vlm_gemv_bf16 (M in {1, 2, 4, 8}).
+ * With norm_w these forms take K <= 8192 (K % 128 == 0; past one K segment the RMSNorm runs as one rows launch into the
+ * workspace), and past K = 4096 the qkv form takes 8 rows as well as 9..16.  A projection of more than 4096 (row tile, K
+ * segment) units - N / 16 tiles times ceil(K / 3072) - is refused (2): the engine cuts such an N into slices of W's rows. */
 size_t vlm_gemv_workspace_bytes(void);
 int vlm_gemv_bf16_ws(const void* x, const void* W, const void* bias, const void* res, const void* norm_w, void* y, int M, int N,
                      int K, int ldx, int ldw, int ldy, int ldres, float eps, int epilogue, void* workspace, void* stream);
@@ -128,7 +138,8 @@ int vlm_gemv_attn_out(const void* part_o, const void* part_ml, int nsplit, const
  * Engine layout (repacked once at load): Wq uint32 [N][K/8], MLX's own words (element k of a row in word k / 8, bits
  * 4 (k % 8) .. +3); Wsb uint32 [N][K/64] = scale bf16 (low half) | bias bf16 (high half) of each group.  K % 64 == 0.
  * vlm_gemv_w4 / vlm_gemv_w4_qkv_rope_kvwrite: the decode GEMVs of vlm_gemv_bf16 / vlm_gemv_qkv_rope_kvwrite with the
- *   dequantisation fused into the operand path (fp32 affine form per group, no weight is rounded); M in {1,2,4,8}.
+ *   dequantisation fused into the operand path (fp32 affine form per group, no weight is rounded); M in {1,2,4,8};
+ *   K <= 30720 (K <= 4096 with norm_w; hidden <= 8192 for the qkv form) and M * K * 2 + 256 bytes of staged rows <= 160 KiB.
  * vlm_dequant_w4: rows of the matrix as bf16 (fp32 scale * q + bias, one rounding): rows == NULL -> rows 0..n_rows-1
  *   (prefill: materialised once per projection, then vlm_gemm_bf16), rows != NULL -> gather (QuantizedEmbedding lookup).
  *   n_table_rows == -1 is the QUANTISE direction, mx.quantize(w, group_size=64, bits=4) as `mlx_vlm.convert -q` runs it
@@ -470,7 +481,8 @@ int vlm_sample_greedy_advance(const void* logits, int ld, int B, int V, void* lo
  * mlx_vlm/generate/ar.py:474-508).
  * ------------------------------------------------------------------------------------------ */
 typedef struct vlm_llm_config {
-  int hidden, n_layers, inter, n_heads, n_kv_heads, head_dim, vocab;
+  int hidden /* <= 8192; a multiple of 128 above 4096 (vlm_llm_create returns 2 otherwise, before anything is allocated) */,
+      n_layers, inter, n_heads, n_kv_heads, head_dim, vocab;
   float rms_eps;
   int mrope_sec0, mrope_sec1; /* mrope_section[0], [1] */
   float attn_scale;           /* softmax scale of the attention; 0 = head_dim ** -0.5.  Set when the engine's head_dim is a

@@ -113,6 +113,9 @@ struct Vit {
 
 inline char* off(void* p, size_t bytes) { return static_cast<char*>(p) + bytes; }
 
+constexpr int VLM_ERR_SHAPE = 2;        // "unsupported shape" of include/vlm_hip.h: the launcher enqueued nothing
+constexpr int VLM_MAX_HIDDEN = 8192;    // widest residual stream (vlm_llm_create)
+
 }  // namespace
 
 extern "C" int vlm_abi_version(void) { return 8; }
@@ -121,6 +124,9 @@ extern "C" int vlm_abi_version(void) { return 8; }
 extern "C" int vlm_llm_create(const vlm_llm_config* cfg, void** handle) {
   if (!cfg || !handle) return 1;
   if (cfg->hidden <= 0 || cfg->n_layers <= 0 || cfg->n_heads <= 0 || cfg->n_kv_heads <= 0 || cfg->head_dim <= 0) return 1;
+  // widest residual stream: 8192 columns (Qwen2-VL-72B) - the RMSNorm kernels, the staged rows of the decode GEMVs and the
+  // workspace's normalised rows (VLM_MFMA_WS_XN_BYTES) end there; past 4096 the 128-wide K chunks of the matrix-core forms
+  if (cfg->hidden > VLM_MAX_HIDDEN || (cfg->hidden > 4096 && cfg->hidden % 128 != 0)) return VLM_ERR_SHAPE;
   Llm* m = new (std::nothrow) Llm();
   if (!m) return 1;
   m->cfg = *cfg;
@@ -255,12 +261,54 @@ static int lin_gemm_tail(Llm* m, const void* A, const void* W, const void* Wsb, 
   if (Wsb) return lin_gemm(m, A, W, Wsb, bias, res, C, M, N, K, ldc, ldres, epi, stream);
   return vlm_gemm_bf16_tail(A, W, bias, res, C, M, N, K, K, K, ldc, ldres, epi, tail, done, stream);
 }
-// decode: y = epi(x . W^T) for B rows
-static int lin_gemv(Llm* m, const void* x, const void* W, const void* Wsb, const void* bias, const void* res, const void* norm_w,
-                    void* y, int B, int N, int K, int ldy, int ldres, float eps, int epi, void* stream) {
+// decode: y = epi(x . W^T) for B rows, one launch
+static int lin_gemv1(Llm* m, const void* x, const void* W, const void* Wsb, const void* bias, const void* res, const void* norm_w,
+                     void* y, int B, int N, int K, int ldy, int ldres, float eps, int epi, void* stream) {
   if (Wsb) return vlm_gemv_w4_ex(x, W, Wsb, bias, res, norm_w, y, B, N, K, K, ldy, ldres, eps, epi, m->tune.mfma_gemv, m->mfma_ws, stream);
   // B >= 3: batch rows on the matrix cores (gemv_mfma.hip), K split over workgroups through the engine's workspace
   return vlm_gemv_bf16_ex(x, W, bias, res, norm_w, y, B, N, K, K, K, ldy, ldres, eps, epi, m->tune.mfma_gemv, m->mfma_ws, stream);
+}
+// ... and what a decode step does when no form takes the projection in one launch (VLM_ERR_SHAPE: nothing was enqueued; before
+// hidden sizes past 4096 such a step failed).  The same values from launches that exist:
+//   - a norm prologue nobody takes runs as vlm_rmsnorm_residual into `xn` (B rows of K columns, may be NULL: then refused) and
+//     the projection without a prologue.  Past K = 4096 this IS the form of the 1 / 2 / 4-row steps (bf16: every norm-prologue
+//     projection; 4-bit: gate/up and the head): measured at K = 8192 the pair beat a fused kernel;
+//   - more than 16384 output rows (72B gate/up: 59136, the head: 152064) are cut into slices of W's rows - a slice fits the 4096
+//     (row tile, K segment) units of the matrix-core forms' workspace at any K <= 8192;
+//   - rows no kernel takes together (4 rows of the 72B down projection's K = 29568 over 4-bit weights exceed a workgroup's
+//     staged activations; a row count or K the matrix-core forms refuse) run as two launches of floor / ceil half the rows.
+// *more counts the launches beyond the first.
+static int lin_gemv(Llm* m, const void* x, const void* W, const void* Wsb, const void* bias, const void* res, const void* norm_w,
+                    void* y, int B, int N, int K, int ldy, int ldres, float eps, int epi, void* xn, int* more, void* stream) {
+  const int rc = lin_gemv1(m, x, W, Wsb, bias, res, norm_w, y, B, N, K, ldy, ldres, eps, epi, stream);
+  if (rc != VLM_ERR_SHAPE || (epi & (VLM_EPI_X_TILED | VLM_EPI_Y_TILED))) return rc;
+  if (norm_w) {
+    if (!xn) return rc;
+    TRY(vlm_rmsnorm_residual(x, nullptr, norm_w, xn, nullptr, B, K, eps, stream));
+    ++*more;
+    return lin_gemv(m, xn, W, Wsb, bias, res, nullptr, y, B, N, K, ldy, ldres, 0.f, epi, nullptr, more, stream);
+  }
+  constexpr int SL = 16384;
+  if (N > SL) {
+    for (int n0 = 0; n0 < N; n0 += SL) {
+      const int nn = N - n0 < SL ? N - n0 : SL;
+      const void* Ws = off(const_cast<void*>(W), Wsb ? (size_t)n0 * K / 2 : (size_t)n0 * K * 2);
+      const void* sbs = Wsb ? off(const_cast<void*>(Wsb), (size_t)n0 * (K / 64) * 4) : nullptr;
+      TRY(lin_gemv(m, x, Ws, sbs, bias ? off(const_cast<void*>(bias), (size_t)n0 * 2) : nullptr,
+                   res ? off(const_cast<void*>(res), (size_t)n0 * 2) : nullptr, nullptr,
+                   off(y, (size_t)((epi & VLM_EPI_SWIGLU) ? n0 / 2 : n0) * 2), B, nn, K, ldy, ldres, 0.f, epi, nullptr, more, stream));
+      if (n0) ++*more;
+    }
+    return 0;
+  }
+  if (B > 1) {      // rows [0, h) and [h, B): any row count comes down to the 1 / 2 / 4 / 8-row kernels
+    const int h = B / 2;
+    TRY(lin_gemv(m, x, W, Wsb, bias, res, nullptr, y, h, N, K, ldy, ldres, 0.f, epi, nullptr, more, stream));
+    ++*more;
+    return lin_gemv(m, off(const_cast<void*>(x), (size_t)h * K * 2), W, Wsb, bias, res ? off(const_cast<void*>(res), (size_t)h * ldres * 2) : nullptr,
+                    nullptr, off(y, (size_t)h * ldy * 2), B - h, N, K, ldy, ldres, 0.f, epi, nullptr, more, stream);
+  }
+  return rc;
 }
 
 extern "C" int vlm_llm_prefill(void* handle, const vlm_prefill_args* a, void* stream) {
@@ -362,6 +410,8 @@ static int decode_impl(Llm* m, const vlm_decode_args* a, void* stream, int* laun
   const bool wide = B > 16;
   if (wide && (!m->kv.block_table || Hq * hd < D || B > 64)) return 1;
   void* const xn = a->attn;
+  // ... and so does a narrow step whose norm-prologue projection no one-launch form takes (lin_gemv), where the buffer holds a row
+  void* const xn_rows = Hq * hd >= D ? a->attn : nullptr;
   bool xn_ready = false;      // wide steps: xn already holds RMSNorm(h) of the coming layer (the previous down GEMM's reduce launch wrote it)
   int n = 0;
   // h = embed[tok]
@@ -396,14 +446,24 @@ static int decode_impl(Llm* m, const vlm_decode_args* a, void* stream, int* laun
         TRY(vlm_mrope_kvwrite_decode(a->qkv, QKV, B, Hq, Hkv, hd, a->pos, m->g.inv_freq, c.mrope_sec0, c.mrope_sec1, slot,
                                      m->kv.block_table, m->kv.max_pages, kp, vp, qk_scale, c.rope_long_from, stream)); ++n;
       }
-    } else if (w.wqkv_sb) {
-      TRY(vlm_gemv_w4_qkv_rope_kvwrite_ex(a->h, w.ln1_w, c.rms_eps, w.wqkv, w.wqkv_sb, w.bqkv, a->qkv, QKV, B, D, Hq, Hkv, hd, a->pos,
-                                          slot, m->g.inv_freq, m->kv.block_table, m->kv.max_pages, kp, vp, m->tune.mfma_gemv,
-                                          m->mfma_ws, qk_scale, c.rope_long_from, stream)); ++n;
     } else {
-      TRY(vlm_gemv_qkv_rope_kvwrite_ex(a->h, w.ln1_w, c.rms_eps, w.wqkv, w.bqkv, a->qkv, QKV, B, D, Hq, Hkv, hd, a->pos, slot,
-                                       m->g.inv_freq, m->kv.block_table, m->kv.max_pages, kp, vp, m->tune.mfma_gemv, m->mfma_ws,
-                                       qk_scale, c.rope_long_from, stream)); ++n;
+      const int rc = w.wqkv_sb
+          ? vlm_gemv_w4_qkv_rope_kvwrite_ex(a->h, w.ln1_w, c.rms_eps, w.wqkv, w.wqkv_sb, w.bqkv, a->qkv, QKV, B, D, Hq, Hkv, hd, a->pos,
+                                            slot, m->g.inv_freq, m->kv.block_table, m->kv.max_pages, kp, vp, m->tune.mfma_gemv,
+                                            m->mfma_ws, qk_scale, c.rope_long_from, stream)
+          : vlm_gemv_qkv_rope_kvwrite_ex(a->h, w.ln1_w, c.rms_eps, w.wqkv, w.bqkv, a->qkv, QKV, B, D, Hq, Hkv, hd, a->pos, slot,
+                                         m->g.inv_freq, m->kv.block_table, m->kv.max_pages, kp, vp, m->tune.mfma_gemv, m->mfma_ws,
+                                         qk_scale, c.rope_long_from, stream);
+      if (rc == 0) ++n;      // (a refused launcher enqueued nothing)
+      if (rc == VLM_ERR_SHAPE && xn_rows) {
+        // no one-launch form for this (rows, hidden): the wide steps' sequence - RMSNorm, projection + bias, M-RoPE + KV write
+        TRY(lin_gemv(m, a->h, w.wqkv, w.wqkv_sb, w.bqkv, nullptr, w.ln1_w, a->qkv, B, QKV, D, QKV, 0, c.rms_eps,
+                     w.bqkv ? VLM_EPI_BIAS : VLM_EPI_NONE, xn_rows, &n, stream)); ++n;      // (the projection; lin_gemv counted the rest)
+        TRY(vlm_mrope_kvwrite_decode(a->qkv, QKV, B, Hq, Hkv, hd, a->pos, m->g.inv_freq, c.mrope_sec0, c.mrope_sec1, slot,
+                                     m->kv.block_table, m->kv.max_pages, kp, vp, qk_scale, c.rope_long_from, stream)); ++n;
+      } else if (rc != 0) {
+        return rc;
+      }
     }
     // attention over the pages (the new token is already in the cache: kv_len = ctx + 1)
     // combine: the split partials are merged by the attention side (combine kernel / last arriver) into a->attn - 4-bit Wo,
@@ -480,7 +540,7 @@ static int decode_impl(Llm* m, const vlm_decode_args* a, void* stream, int* laun
     if (merge_in_oproj) {
       TRY(vlm_gemv_attn_out_bf16(a->part_o, a->part_ml, psplit | ml_pitch, w.wo, a->h, D, D, Hq, hd, stream)); ++n;
     } else if (psplit || a->nsplit == 1 || combine) {
-      TRY(lin_gemv(m, a->attn, w.wo, w.wo_sb, nullptr, a->h, nullptr, a->h, B, D, Hq * hd, D, D, 0.f, VLM_EPI_RESIDUAL, stream)); ++n;
+      TRY(lin_gemv(m, a->attn, w.wo, w.wo_sb, nullptr, a->h, nullptr, a->h, B, D, Hq * hd, D, D, 0.f, VLM_EPI_RESIDUAL, nullptr, &n, stream)); ++n;
     } else {
       TRY(vlm_gemv_attn_out(a->part_o, a->part_ml, a->nsplit, w.wo, a->h, D, B, D, Hq, hd, stream)); ++n;
     }
@@ -490,15 +550,15 @@ static int decode_impl(Llm* m, const vlm_decode_args* a, void* stream, int* laun
     bool tiled = false;
     if ((a->flags & VLM_DECODE_ACT16) && B >= 5 && tn.mfma_gemv && !w.wgu_sb && !w.wdown_sb && vlm_gemv_mfma_rows_ok(B, D, c.inter) &&
         c.inter % 8 == 0) {
-      const int rc = lin_gemv(m, a->h, w.wgu, nullptr, nullptr, nullptr, w.ln2_w, a->act, B, 2 * c.inter, D, c.inter, 0, c.rms_eps,
-                              VLM_EPI_SWIGLU | VLM_EPI_Y_TILED, stream);
+      const int rc = lin_gemv1(m, a->h, w.wgu, nullptr, nullptr, nullptr, w.ln2_w, a->act, B, 2 * c.inter, D, c.inter, 0, c.rms_eps,
+                               VLM_EPI_SWIGLU | VLM_EPI_Y_TILED, stream);
       if (rc == 0) tiled = true;
       else if (rc != 2) return rc;
     }
-    if (!tiled) TRY(lin_gemv(m, a->h, w.wgu, w.wgu_sb, nullptr, nullptr, w.ln2_w, a->act, B, 2 * c.inter, D, c.inter, 0, c.rms_eps, VLM_EPI_SWIGLU, stream));
+    if (!tiled) TRY(lin_gemv(m, a->h, w.wgu, w.wgu_sb, nullptr, nullptr, w.ln2_w, a->act, B, 2 * c.inter, D, c.inter, 0, c.rms_eps, VLM_EPI_SWIGLU, xn_rows, &n, stream));
     ++n;
     TRY(lin_gemv(m, a->act, w.wdown, w.wdown_sb, nullptr, a->h, nullptr, a->h, B, D, c.inter, D, D, 0.f,
-                 VLM_EPI_RESIDUAL | (tiled ? VLM_EPI_X_TILED : 0), stream)); ++n;
+                 VLM_EPI_RESIDUAL | (tiled ? VLM_EPI_X_TILED : 0), nullptr, &n, stream)); ++n;
   }
   // logits = RMSNorm(h) lm_head^T
   const int VL = (c.vocab + 7) & ~7;      // row pitch of logits / logprobs / scratch (see vlm_llm_prefill)
@@ -508,7 +568,7 @@ static int decode_impl(Llm* m, const vlm_decode_args* a, void* stream, int* laun
     TRY(lin_gemm(m, xn, m->g.lm_head, m->g.lm_head_sb, nullptr, nullptr, a->logits, B, VL, D, VL, 0, VLM_EPI_NONE, stream)); ++n;
   } else {
     TRY(lin_gemv(m, a->h, m->g.lm_head, m->g.lm_head_sb, nullptr, nullptr, m->g.final_norm_w, a->logits, B, c.vocab, D, VL, 0,
-                 c.rms_eps, VLM_EPI_NONE, stream)); ++n;
+                 c.rms_eps, VLM_EPI_NONE, xn_rows, &n, stream)); ++n;
   }
   if (sample && a->penalties) {
     // logits processors (ar.py:360-364): the fed token joins the history, then bias / penalties on the step's logits

@@ -542,6 +542,21 @@ __global__ __launch_bounds__(256) void gemv_splitk_kernel(const bf16_t* __restri
       if (lane == 0) red[wave][r][m] = s;
     }
   __syncthreads();
+  if (EPI & VLM_EPI_SWIGLU) {
+    // rows (2 j, 2 j + 1) are gate j / up j: a workgroup holds whole pairs (RW even), one thread per (pair, batch row); the
+    // rounding points of the row-wave kernel's SwiGLU epilogue
+    static_assert(!(EPI & VLM_EPI_SWIGLU) || RW % 2 == 0, "gate / up pairs stay in one workgroup");
+    if (tid < (RW / 2) * MB) {
+      const int r = 2 * (tid / MB), m = tid % MB;
+      if (row0 + r + 1 < N) {
+        const float g = red[0][r][m] + red[1][r][m] + red[2][r][m] + red[3][r][m];
+        const float u = red[0][RW > 1 ? r + 1 : 0][m] + red[1][RW > 1 ? r + 1 : 0][m] + red[2][RW > 1 ? r + 1 : 0][m] +
+                        red[3][RW > 1 ? r + 1 : 0][m];
+        y[(size_t)m * ldy + ((row0 + r) >> 1)] = f2bf(swiglu_(rbf(g), rbf(u)));
+      }
+    }
+    return;
+  }
   if (tid < RW * MB) {
     const int r = tid / MB, m = tid % MB;
     if (row0 + r < N) {
@@ -645,14 +660,20 @@ int launch_sk_k(const Args& a) {
     // 72 KB: the launch ends with the loaded half); 6 rows = ONE 107 KB workgroup per CU, 3 rows = two per CU
     if constexpr (MB == 1) {
       if (ni <= 5 && (g_gemv_variant & 1) && a.N % 6 == 0) return launch_sk<6, 5, MB, EPI>(a);
-      if (ni <= 5 && (g_gemv_variant & 2) && a.N % 3 == 0) return launch_sk<3, 5, MB, EPI>(a);
+      if constexpr (!(EPI & VLM_EPI_SWIGLU))
+        if (ni <= 5 && (g_gemv_variant & 2) && a.N % 3 == 0) return launch_sk<3, 5, MB, EPI>(a);
     }
     if (ni <= 5) return launch_sk<4, 5, MB, EPI>(a);
     if (ni <= 10) return launch_sk<2, 10, MB, EPI>(a);
   } else {
     if (ni <= 5) return launch_sk<2, 5, MB, EPI>(a);
-    if (ni <= 10) return launch_sk<1, 10, MB, EPI>(a);
+    if constexpr (!(EPI & VLM_EPI_SWIGLU))      // (one row per workgroup: no gate / up pair)
+      if (ni <= 10) return launch_sk<1, 10, MB, EPI>(a);
   }
+  // K <= 30720: the 72B down projection (29568), up to 4 rows (8 rows of 15 chunks do not fit the registers: the
+  // matrix-core forms take those)
+  if constexpr (MB <= 4 && !(EPI & VLM_EPI_SWIGLU))
+    if (ni <= 15) return launch_sk<1, 15, MB, EPI>(a);
   return VLM_ERR_SHAPE;
 }
 
@@ -739,11 +760,14 @@ VLM_INTERNAL int vlm_gemv_bf16_ex(const void* x, const void* W, const void* bias
     }
 #undef GO
   }
-  if (norm_w) return VLM_ERR_SHAPE;   // the norm prologue needs the row-wave kernel (K <= 3584)
+  // the norm prologue needs the row-wave kernel (K <= 4096).  Past that the caller runs vlm_rmsnorm_residual and this
+  // kernel: measured at K = 8192 a 16-chunk row-wave form lost to that pair on every launch
+  if (norm_w) return VLM_ERR_SHAPE;
   switch (epilogue) {
     case VLM_EPI_NONE: return launch_sk_m<VLM_EPI_NONE>(M, a);
     case VLM_EPI_BIAS: return launch_sk_m<VLM_EPI_BIAS>(M, a);
     case VLM_EPI_RESIDUAL: return launch_sk_m<VLM_EPI_RESIDUAL>(M, a);
+    case VLM_EPI_SWIGLU: return launch_sk_m<VLM_EPI_SWIGLU>(M, a);
     default: return VLM_ERR_ARG;
   }
 }

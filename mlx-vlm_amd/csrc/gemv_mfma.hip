@@ -621,7 +621,8 @@ static int mfma_try(const void* x, const void* W, const void* Wsb, const void* b
   static const int min_m = [] { const char* e = getenv("VLM_GEMV_MFMA_MIN_M"); return e ? atoi(e) : 5; }();
   const bool y_tiled = (epilogue & VLM_EPI_Y_TILED) != 0;      // (this form's epilogue writes it; the other forms are skipped)
   epilogue &= ~VLM_EPI_Y_TILED;
-  if (!enabled || M < (rk ? max(min_m, 9) : min_m) || M > 16 || K % 128 || ldx % 8 || ldw % 8) return -1;
+  // (past K = 4096 the qkv form takes 8 rows as well: the v_dot2c kernels stage at most 64 KiB of rows - 4 of 8192 - per workgroup)
+  if (!enabled || M < (rk ? max(min_m, K > 4096 ? 8 : 9) : min_m) || M > 16 || K % 128 || ldx % 8 || ldw % 8) return -1;
   const bool rope = rk != nullptr;
   if (y_tiled && (rope || Wsb)) return -1;
   if (rope && (rk->D % 16 || !norm_w || !bias)) return -1;

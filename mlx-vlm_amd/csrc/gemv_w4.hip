@@ -120,7 +120,9 @@ __global__ __launch_bounds__(256) void gemv_w4_kernel(const bf16_t* __restrict__
   // ---- activation rows -> LDS as bf16 in pair order (normalised when PRO_RMSNORM): x and the norm weight are read ONCE
   //      (one global round trip), the sum of squares comes from the registers
   float* red = reinterpret_cast<float*>(smem + (size_t)MB * K * 2);
-  constexpr int XCH = KC >= 2 ? 2 : 1;       // norm prologue: K <= 4096 (checked by the launcher); KC == 1 <=> K <= 2048
+  // norm prologue: K <= 8192 (checked by the launcher); KC == 1 <=> K <= 2048, KC == 2 <=> K <= 4096, 4 chunks of 8 per thread
+  // beyond (8 rows of 8192: 128 VGPRs of x and 128 KiB of staged rows - one workgroup per CU walks its row groups)
+  constexpr int XCH = KC >= 5 ? 4 : KC >= 2 ? 2 : 1;
   if (PRO == WPRO_RMSNORM) {
     uint4 xv[MB][XCH], wv[XCH];
 #pragma unroll
@@ -380,6 +382,8 @@ int w4_k(const W4Args& a) {
   if (a.K <= 4096) return w4_rows<2, MB, PRO, EPI>(a);
   if (a.K <= 10240) return w4_rows<5, MB, PRO, EPI>(a);
   if (a.K <= 20480) return w4_rows<10, MB, PRO, EPI>(a);
+  if constexpr (PRO == WPRO_NONE)
+    if (a.K <= 30720) return w4_rows<15, MB, PRO, EPI>(a);      // the 72B down projection (29568)
   return VLM_ERR_SHAPE;
 }
 
@@ -430,7 +434,10 @@ VLM_INTERNAL int vlm_gemv_w4_ex(const void* x, const void* Wq, const void* Wsb, 
   if (K % 64 != 0 || ldx % 8 != 0) return VLM_ERR_SHAPE;
   if ((epilogue & VLM_EPI_SWIGLU) && (N % 2 != 0)) return VLM_ERR_SHAPE;
   if ((size_t)M * K * 2 + 256 > 160 * 1024) return VLM_ERR_SHAPE;
-  if (norm_w && K > 4096) return VLM_ERR_SHAPE;      // the norm prologue keeps x in registers: 2 chunks per thread
+  // the norm prologue keeps x in registers, 2 chunks per thread.  Past K = 4096 the caller runs vlm_rmsnorm_residual and this
+  // kernel without a prologue (measured at K = 8192: the pair is as fast at 1 row and faster at 4 - DESIGN.md section 4);
+  // only the qkv form below, which saves two launches, keeps its prologue there (4 chunks per thread, K <= 8192)
+  if (norm_w && K > 4096) return VLM_ERR_SHAPE;
   W4Args a{x, Wq, Wsb, bias, res, norm_w, y, N, K, ldx, ldy, ldres, eps, W4RopeKv{}, (hipStream_t)stream};
 #define GO(P, E) return w4_m<P, E>(M, a)
   if (norm_w) {
@@ -474,7 +481,7 @@ VLM_INTERNAL int vlm_gemv_w4_qkv_rope_kvwrite_ex(const void* h, const void* norm
                                         VLM_EPI_BIAS, &rk, ws, stream);
     if (rc >= 0) return rc;
   }
-  if (hidden % 64 || hidden > 4096 || D % 16 || (size_t)M * hidden * 2 > 64 * 1024) return VLM_ERR_SHAPE;
+  if (hidden % 64 || hidden > 8192 || D % 16 || (size_t)M * hidden * 2 > (hidden > 4096 ? 128 : 64) * 1024) return VLM_ERR_SHAPE;
   const int N = (Hq + 2 * Hkv) * D;
   W4Args a{h, Wq, Wsb, bqkv, nullptr, norm_w, qkv, N, hidden, hidden, ldq, 0, eps,
            W4RopeKv{(const int*)pos, (const int*)slot, (const float*)inv_freq, (const int*)block_table, max_pages, Hq, Hkv, D,

@@ -62,6 +62,9 @@ __global__ __launch_bounds__(256) void rope2d_vision_kernel(bf16_t* __restrict__
 
 // One thread = one 8-wide chunk of the low half of a q/k head (+ its partners
 // in the high half), or one 8-wide chunk of a v head (copy to the cache).
+// IDENT: no block table - the identity layout of the decode step's fused qkv kernels (sequence s owns pages
+// [s * max_pages, (s + 1) * max_pages)): vlm_mrope_kvwrite_decode behind a narrow step's qkv projection.
+template <bool IDENT>
 __global__ __launch_bounds__(256) void mrope_kvwrite_kernel(
     bf16_t* __restrict__ qkv, int ld, int T, int Hq, int Hkv, int D, const int* __restrict__ pos_t,
     const int* __restrict__ pos_h, const int* __restrict__ pos_w, const float* __restrict__ inv_freq, int sec0, int sec1,
@@ -90,7 +93,7 @@ __global__ __launch_bounds__(256) void mrope_kvwrite_kernel(
   if (kpool) {
     const int seq = kv_seq ? kv_seq[tok] : tok;
     const int slot = kv_slot[tok];
-    page = block_table[(size_t)seq * max_pages + (slot >> 6)];
+    page = IDENT ? (long)seq * max_pages + (slot >> 6) : block_table[(size_t)seq * max_pages + (slot >> 6)];
     within = slot & 63;
   }
 
@@ -211,7 +214,7 @@ extern "C" int vlm_mrope_kvwrite_scaled(void* qkv, int ld, int T, int Hq, int Hk
   if (D % 16 != 0 || ld % 8 != 0) return VLM_ERR_SHAPE;
   if (T == 0) return VLM_OK;
   const long total = (long)T * ((Hq + Hkv) * (D / 16) + Hkv * (D / 8));
-  hipLaunchKernelGGL(mrope_kvwrite_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(mrope_kvwrite_kernel<false>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                      (bf16_t*)qkv, ld, T, Hq, Hkv, D, (const int*)pos_t, (const int*)pos_h, (const int*)pos_w,
                      (const float*)inv_freq, sec0, sec1, (const int*)kv_seq, (const int*)kv_slot,
                      (const int*)block_table, max_pages, (bf16_t*)kpool, (bf16_t*)vpool, qk_scale, 0);
@@ -225,11 +228,19 @@ extern "C" int vlm_mrope_kvwrite_scaled(void* qkv, int ld, int T, int Hq, int Hk
 int vlm_mrope_kvwrite_decode(void* qkv, int ld, int B, int Hq, int Hkv, int D, const void* pos, const void* inv_freq, int sec0,
                              int sec1, const void* slot, const void* block_table, int max_pages, void* kpool, void* vpool,
                              float qk_scale, int long_from, void* stream) {
-  if (!qkv || !pos || !inv_freq || !slot || !block_table || !kpool || !vpool || B <= 0 || B > 64 || Hq <= 0 || Hkv <= 0 || max_pages <= 0)
+  if (!qkv || !pos || !inv_freq || !slot || !kpool || !vpool || B <= 0 || B > 64 || Hq <= 0 || Hkv <= 0 || max_pages <= 0)
     return VLM_ERR_ARG;
   if (D % 16 != 0 || ld % 8 != 0) return VLM_ERR_SHAPE;
   const long total = (long)B * ((Hq + Hkv) * (D / 16) + Hkv * (D / 8));
-  hipLaunchKernelGGL(mrope_kvwrite_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+  if (!block_table) {      // identity layout (the rows of a narrow decode step over a pool that has no table)
+    hipLaunchKernelGGL(mrope_kvwrite_kernel<true>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                       (bf16_t*)qkv, ld, B, Hq, Hkv, D, (const int*)pos, (const int*)pos, (const int*)pos, (const float*)inv_freq,
+                       sec0, sec1, (const int*)nullptr, (const int*)slot, (const int*)nullptr, max_pages, (bf16_t*)kpool,
+                       (bf16_t*)vpool, qk_scale, long_from);
+    VLM_CHECK_LAUNCH();
+    return VLM_OK;
+  }
+  hipLaunchKernelGGL(mrope_kvwrite_kernel<false>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                      (bf16_t*)qkv, ld, B, Hq, Hkv, D, (const int*)pos, (const int*)pos, (const int*)pos, (const float*)inv_freq,
                      sec0, sec1, (const int*)nullptr, (const int*)slot, (const int*)block_table, max_pages, (bf16_t*)kpool,
                      (bf16_t*)vpool, qk_scale, long_from);

@@ -205,10 +205,16 @@ class LanguageModel:
     # WIDE steps on the prefill GEMMs (needs the caller's block table; not for two-table RoPE models: phi3_v sets 16)
     MAX_DECODE_ROWS = 64
 
+    # widest residual stream the engine runs (vlm_llm_create: Qwen2-VL-72B's 8192; multiples of 128 past 4096)
+    MAX_HIDDEN = 8192
+
     supports_logits_to_keep = True
 
     def __init__(self, args: TextConfig, config: ModelConfig, device="cuda", kv_pool_tokens: int = 32768,
                  max_seqs: int = 64, kv_layout: str = "auto"):
+        if args.hidden_size > self.MAX_HIDDEN or (args.hidden_size > 4096 and args.hidden_size % 128):
+            raise NotImplementedError(f"hidden_size = {args.hidden_size}: the engine is built for hidden sizes up to {self.MAX_HIDDEN} "
+                                      "(multiples of 128 above 4096)")
         self.args = args
         self.config = config
         self.model_type = args.model_type
