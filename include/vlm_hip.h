@@ -684,15 +684,25 @@ int vlm_llm_decode_launches(void* handle);
                                        of a head as ceil(S / 2) 16-byte loads where part_ml has an even per-head pitch (an odd one
                                        keeps the forms of bit 11); the Python layer names the page count of a one-row greedy
                                        step's context in VLM_DECODE_NSPLITS_SHIFT of its flags.
+                                       bit 6 (64): the qkv launch of a ONE-row step at hidden <= 1536 and Hq * D <= 1536 takes (Hq, Hkv, D)
+                                       and long_from from a preloaded argument slot and pos / slot / inv_freq by scalar loads:
+                                       nothing is waited for ahead of its weight stream (more rows and wider heads keep their entry).
+                                       bit 13 (8192): the log-sum-exp partials of the sampler (greedy tail and vlm_sample) load a
+                                       thread's elements once and keep them in registers across the max and the sum pass
+                                       (V <= 163,840; a longer row takes the two-pass loop) - same element-to-thread assignment, same
+                                       order of every max and add.
+                                       bit 14 (16384): the fused greedy tail (vlm_sample_greedy_advance) issues the logits loads of a
+                                       thread's first two trips ahead of the loads of the partials, and with one row the block that
+                                       takes the last row ticket is the last block: no second ticket level.
                                        A row's sum does not depend on the rows its wave owns, an output tile not on the
                                        workgroup that owns it, a merge not on slots that hold no page: every bit gives the same
                                        bytes.
                                        Measured (profiles/decode_slack_ab.txt, profiles/latency_launches_ab.txt,
-                                       profiles/split_classes_ab.txt, profiles/split_exact_ab.txt): bits 0, 2, 3, 9, 11, 12 win - the Python layer sets 6669 - bit 4
-                                       loses 1.7 %, bit 5 changes nothing, bit 8 gains half of bit 9; bits 6, 7 and 10 are unused:
-                                       a qkv form with no scalar-load wait ahead of its weights (+0.6 %, under the bar), the o_proj
-                                       in three-wave workgroups (-0.7 %) and the greedy tail's log-sum-exp partials written by the
-                                       head GEMV (-0.5 %) were measured on them and left the library) */
+                                       profiles/split_classes_ab.txt, profiles/split_exact_ab.txt, profiles/decode_tail_entry_ab.txt): bits 0, 2, 3, 9, 11, 12 win,
+                                       bit 6 wins alone, bit 13 as part of the whole step - the Python layer sets 14925 - bit 14 gains nothing measurable, bit 4
+                                       loses 1.7 %, bit 5 changes nothing, bit 8 gains half of bit 9; bits 7 and 10 are unused:
+                                       the o_proj in three-wave workgroups (-0.7 %) and the greedy tail's log-sum-exp partials
+                                       written by the head GEMV (-0.5 %) were measured on them and left the library) */
 #define VLM_TUNE_ATTN_MERGE 9       /* where the page-split attention of a ONE-row step is merged: 1 (default) = in the o_proj
                                        GEMV's prologue (partial-only attention launch, vlm_gemv_attn_out_bf16; needs bf16 Wo,
                                        Hq * D <= 2048, <= 16 splits), 0 = by the attention launch's last-arriving workgroup */

@@ -178,6 +178,7 @@ extern "C" int vlm_llm_set_tuning(void* handle, int key, int value) {
   }
   if (key == VLM_TUNE_GEMV_VARIANT) {
     vlm_gemv_set_variant(value);
+    vlm_sample_set_variant(value);
     vlm_attn_set_dsplit((value & 512) ? 4 : (value & 256) ? 2 : 1);
   }
   if (*slot == value) return 0;

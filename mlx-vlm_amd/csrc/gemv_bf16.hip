@@ -53,6 +53,12 @@ constexpr int ps_slots(int pro) {
   return ps_exact(pro) ? pro - PRO_ATTN_PS_BASE : pro == PRO_ATTN_PS4 ? 4 : pro == PRO_ATTN_PS8 ? 8 : pro == PRO_ATTN_PS12 ? 12 : VLM_MERGE_S;
 }
 constexpr int EPI_ROPE_KV = 1 << 10;   // internal epilogue id (qkv projection)
+// EPI_ROPE_KV_S (MB == 1, K <= 1536, variant bit 6): the same epilogue with nothing but the x / norm_w / bias loads ahead of
+// the weight stream.  (Hq, Hkv, D) and long_from arrive in the preloaded res slot (the qkv form has no residual), so the rows
+// of the weight stream depend on preloaded dwords only; pos[0], slot[0] and inv_freq[rope_j] are wave-uniform and come by
+// SCALAR loads behind the one of RopeKvArgs, waited for at the sincosf that runs while the weights are in flight
+constexpr int EPI_ROPE_KV_S = EPI_ROPE_KV | 1 << 11;
+constexpr bool is_rope_kv(int epi) { return (epi & EPI_ROPE_KV) != 0; }
 
 struct RopeKvArgs {
   const int* pos;            // [M] rope position (all three M-RoPE axes are equal for a decoded text token)
@@ -103,9 +109,11 @@ __device__ __forceinline__ float dot8(const u32x4_t w, const u32x4_t x, float ac
 //   xaux   norm_w [K] bf16 (norm prologues)     | PRO_ATTN_PS: its (m, l) pairs (AttnProArgs::part_ml)
 //   ldx    leading dimension of x               | PRO_ATTN_PS: S | D << 8 (x has no leading dimension: it is the merge);
 //                                               | the exact forms: | P << 24, the per-head pitch of part_ml in (m, l) pairs
+//   res    residual [M][ldres] bf16             | EPI_ROPE_KV_S: Hq | Hkv << 8 | D << 16 (low dword), long_from (high dword)
 // PRO_ATTN (the general merge) keeps reading AttnProArgs.  The qkv form (EPI_ROPE_KV) needs 22 dwords ahead of its weight
 // stream - these plus pos, slot, inv_freq, (Hq, Hkv, D) and long_from of RopeKvArgs: its x / norm_w loads go out on the
-// preloaded arguments and the rest waits for the scalar load behind them (profiles/kernarg_preload.txt).
+// preloaded arguments and the rest waits for the scalar load behind them (profiles/kernarg_preload.txt); the one-row form
+// EPI_ROPE_KV_S waits for nothing (profiles/decode_tail_entry_ab.txt).
 template <int R, int KC, int MB, int PRO, int EPI>
 __global__ __launch_bounds__(256) void gemv_rowwave_kernel(const bf16_t* __restrict__ W, const void* __restrict__ xsrc,
                                                            const void* __restrict__ xaux, const bf16_t* __restrict__ bias,
@@ -120,10 +128,19 @@ __global__ __launch_bounds__(256) void gemv_rowwave_kernel(const bf16_t* __restr
     ap.S = ldx & 255;
     ap.D = ps_exact(PRO) ? (ldx >> 8) & 0xffff : ldx >> 8;
   }
+  if (EPI == EPI_ROPE_KV_S) {
+    static_assert(EPI != EPI_ROPE_KV_S || MB == 1, "one batch row");
+    const unsigned long long pk = reinterpret_cast<unsigned long long>(res);
+    rk.Hq = (int)(pk & 255);
+    rk.Hkv = (int)(pk >> 8 & 255);
+    rk.D = (int)(pk >> 16 & 0xffff);
+    rk.long_from = (int)(pk >> 32);
+  }
   extern __shared__ __attribute__((aligned(16))) char smem[];   // xs[MB][K] bf16
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int nchunk = K >> 3;
-  const int gw = blockIdx.x * 4 + wave;
+  // (EPI_ROPE_KV_S: a wave index the compiler knows to be uniform - rope_j and the weight rows stay on the scalar side)
+  const int gw = blockIdx.x * 4 + (EPI == EPI_ROPE_KV_S ? __builtin_amdgcn_readfirstlane(wave) : wave);
 
   // ---- loads are returned in issue order (vmcnt), so the SMALL latency-critical ones go first: the
   //      activation row for the norm prologue and the epilogue operands; then every weight load of the
@@ -157,13 +174,14 @@ __global__ __launch_bounds__(256) void gemv_rowwave_kernel(const bf16_t* __restr
       if (MB > 4) xv2[c] = *reinterpret_cast<const u32x4_t*>(x + (size_t)(4 + wave) * ldx + (size_t)chc * 8);
     }
   }
-  // ---- which rows does this wave own?  (Behind the norm prologue's loads: in the qkv form the answer needs RopeKvArgs,
-  //      which is not among the preloaded arguments - the x / norm_w loads above go out while its scalar load is in flight)
+  // ---- which rows does this wave own?  (Behind the norm prologue's loads: in the qkv form of EPI_ROPE_KV the answer needs
+  //      RopeKvArgs, which is not among the preloaded arguments - the x / norm_w loads above go out while its scalar load
+  //      is in flight)
   if (EPI == EPI_ROPE_KV) __builtin_amdgcn_sched_barrier(0);
   int row[R];
   bool rope_pair = false;
   int rope_head = 0, rope_j = 0;
-  if (EPI == EPI_ROPE_KV) {
+  if (is_rope_kv(EPI)) {
     const int half = rk.D >> 1, n_pair = (rk.Hq + rk.Hkv) * half;
     if (gw < n_pair) {
       rope_pair = true;
@@ -245,7 +263,10 @@ __global__ __launch_bounds__(256) void gemv_rowwave_kernel(const bf16_t* __restr
   bf16_t e_b0 = 0, e_b1 = 0, e_r = 0;
   int e_pos = 0, e_slot = 0;
   float e_if = 0.f, e_if2 = 0.f;
-  if (EPI == EPI_ROPE_KV) {
+  if (EPI == EPI_ROPE_KV_S) {
+    e_b0 = bias[min(row[0], N - 1)];
+    e_b1 = bias[min(row[R - 1], N - 1)];
+  } else if (EPI == EPI_ROPE_KV) {
     const int mm = min(lane, MB - 1), r0 = min(row[0], N - 1), r1 = min(row[R - 1], N - 1);
     e_b0 = bias[r0];
     e_b1 = bias[r1];
@@ -275,6 +296,14 @@ __global__ __launch_bounds__(256) void gemv_rowwave_kernel(const bf16_t* __restr
     }
   }
   __builtin_amdgcn_sched_barrier(0);
+  if (EPI == EPI_ROPE_KV_S) {
+    // wave-uniform addresses: scalar loads, which do not queue behind the weight stream (the scalar path does not share the
+    // vector memory pipe's in-order return)
+    e_slot = rk.slot[0];
+    e_pos = rk.pos[0];
+    e_if = rk.inv_freq[rope_j];
+    e_if2 = rk.inv_freq[(rk.long_from > 0 ? (rk.D >> 1) : 0) + rope_j];
+  }
 
   // ---- prologue: activation vector(s) -> LDS as bf16
   if (is_norm(PRO)) {
@@ -393,7 +422,7 @@ __global__ __launch_bounds__(256) void gemv_rowwave_kernel(const bf16_t* __restr
   // the critical path of every qkv launch)
   float rope_sn = 0.f, rope_cs = 1.f;
   bool use_long = false;
-  if (EPI == EPI_ROPE_KV) {
+  if (is_rope_kv(EPI)) {
     // lanes >= MB hold row MB - 1's slot again: the vote covers exactly the rows of the step (wave-uniform result)
     use_long = rk.long_from > 0 && __any(e_slot >= rk.long_from);
     sincosf((float)e_pos * (use_long ? e_if2 : e_if), &rope_sn, &rope_cs);
@@ -423,7 +452,7 @@ __global__ __launch_bounds__(256) void gemv_rowwave_kernel(const bf16_t* __restr
 #pragma unroll
     for (int m = 0; m < MB; ++m) acc[r][m] = wave_sum(acc[r][m]);
 
-  if (EPI == EPI_ROPE_KV) {
+  if (is_rope_kv(EPI)) {
     // R == 2: (d, d + D/2) of one q/k head, or two consecutive v rows.  Lane m stores batch row m.
     float a0 = 0.f, a1 = 0.f;
 #pragma unroll
@@ -592,8 +621,12 @@ int launch_rw(const Args& a, int n_waves) {
   const void* xsrc = is_ps(PRO) ? (const void*)a.ap.part_o : a.x;
   const void* xaux = is_ps(PRO) ? (const void*)a.ap.part_ml : a.norm_w;
   const int ldx = is_ps(PRO) ? (a.ap.S | a.ap.D << 8 | (ps_exact(PRO) ? a.ldx << 24 : 0)) : a.ldx;   // (exact forms: a.ldx = P)
+  const void* res = a.res;
+  if (EPI == EPI_ROPE_KV_S)
+    res = reinterpret_cast<const void*>((unsigned long long)(unsigned)(a.rk.Hq | a.rk.Hkv << 8 | a.rk.D << 16) |
+                                        (unsigned long long)(unsigned)a.rk.long_from << 32);
   hipLaunchKernelGGL((gemv_rowwave_kernel<R, KC, MB, PRO, EPI>), dim3(grid), dim3(256), lds, a.st, (const bf16_t*)a.W, xsrc,
-                     xaux, (const bf16_t*)a.bias, (const bf16_t*)a.res, a.N, a.K, a.ldw, ldx, (bf16_t*)a.y, a.ldy, a.ldres,
+                     xaux, (const bf16_t*)a.bias, (const bf16_t*)res, a.N, a.K, a.ldw, ldx, (bf16_t*)a.y, a.ldy, a.ldres,
                      a.eps, a.rk, a.ap);
   return launch_err();
 }
@@ -616,6 +649,12 @@ int launch_rw_r(const Args& a) {
     if (g_gemv_variant & 16) return launch_rw<4, KC, MB, PRO, EPI>(a, vlm_cdiv(a.N, 4));
   if (EPI == EPI_ROPE_KV) {
     const int waves = (a.rk.Hq + a.rk.Hkv) * (a.rk.D / 2) + a.rk.Hkv * a.rk.D / 2;
+    // one row at K <= 1536 and Hq * D <= 1536: the form that waits for no scalar load ahead of its weight stream
+    // ((Hq, Hkv, D) and long_from must fit its packed slot)
+    if constexpr (EPI == EPI_ROPE_KV && MB == 1 && PRO == PRO_RMSNORM && KC == 3)
+      if ((g_gemv_variant & 64) && a.rk.Hq * a.rk.D <= 512 * 3 && a.rk.Hq < 256 && a.rk.Hkv < 256 && a.rk.D < 65536 &&
+          a.rk.long_from >= 0)
+        return launch_rw<2, KC, MB, PRO, EPI_ROPE_KV_S>(a, waves);
     return launch_rw<2, KC, MB, PRO, EPI>(a, waves);
   }
   return launch_rw<2, KC, MB, PRO, EPI>(a, vlm_cdiv(a.N, 2));

@@ -56,6 +56,7 @@ VLM_INTERNAL int vlm_gemv_mfma2_try_w4(const void* x, const void* W, const void*
 VLM_INTERNAL int vlm_gemv_mfma_longk_try(const void* x, const void* W, const void* bias, const void* res, void* y, int M, int N,
                                          int K, int ldx, int ldw, int ldy, int ldres, int epilogue, void* stream);
 VLM_INTERNAL void vlm_gemv_set_variant(int bits);   // A/B bits of the batch-1 launch shapes (process-wide; VLM_TUNE_GEMV_VARIANT)
+VLM_INTERNAL void vlm_sample_set_variant(int bits); // ... its bits 13, 14: the forms of the greedy tail's two launches (sample.hip)
 VLM_INTERNAL int vlm_gemv_attn_out_exact_ok(int K);   // its bit 12: vlm_gemv_attn_out_bf16 has an exact-split form at K = Hq * D
 VLM_INTERNAL void vlm_attn_set_dsplit(int dz);     // its bits 8 / 9: the partial-only page-split attention over 2 / 4 workgroups per page
 VLM_INTERNAL int vlm_gemv_bf16_ex(const void* x, const void* W, const void* bias, const void* res, const void* norm_w, void* y,

@@ -64,6 +64,54 @@ __global__ __launch_bounds__(256) void lse_partial_kernel(const bf16_t* __restri
   if (threadIdx.x == 0) { ws[(size_t)b * ROW_W + blk * 2] = m; ws[(size_t)b * ROW_W + blk * 2 + 1] = s; }
 }
 
+// lse_partial_kernel in ONE pass over memory (VLM_TUNE_GEMV_VARIANT bit 13): thread t still owns elements lo + t + 256 j, but
+// loads all of them - at most LSE_NV, i.e. a slice of per <= 256 LSE_NV elements, V <= 163,840 - before the first use and keeps
+// them in registers across the max pass, the barrier and the sum pass: one memory round trip instead of up to ten dependent
+// trips per pass.  Every fmaxf and every add runs in the order of the loop above (an element past the slice's end is loaded
+// from a clamped address and skipped): the same partial words, bit for bit.  A longer slice takes the loop above.
+constexpr int LSE_NV = 10;
+
+__global__ __launch_bounds__(256) void lse_partial_kernel_regs(const bf16_t* __restrict__ logits, int ld, int V,
+                                                               float* __restrict__ ws) {
+  __shared__ float red[16];
+  const int b = blockIdx.y, blk = blockIdx.x;
+  const int per = ((V + NBLK - 1) / NBLK + 7) & ~7;
+  const int lo = blk * per, hi = min(V, lo + per);
+  const bf16_t* row = logits + (size_t)b * ld;
+  bf16_t v[LSE_NV];
+#pragma unroll
+  for (int j = 0; j < LSE_NV; ++j) v[j] = row[min(lo + (int)threadIdx.x + 256 * j, V - 1)];
+  __builtin_amdgcn_sched_barrier(0);   // every load is out before the first wait
+  float m = -INFINITY;
+#pragma unroll
+  for (int j = 0; j < LSE_NV; ++j)
+    if (lo + (int)threadIdx.x + 256 * j < hi) m = fmaxf(m, bf2f(v[j]));
+  m = wave_max(m);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
+  __syncthreads();
+  m = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+  float s = 0.f;
+  if (m > -INFINITY) {
+#pragma unroll
+    for (int j = 0; j < LSE_NV; ++j)
+      if (lo + (int)threadIdx.x + 256 * j < hi) s += expf(bf2f(v[j]) - m);
+  }
+  s = block_sum(s, red + 4);
+  if (threadIdx.x == 0) { ws[(size_t)b * ROW_W + blk * 2] = m; ws[(size_t)b * ROW_W + blk * 2 + 1] = s; }
+}
+
+// A/B bits of the greedy tail's launches (vlm_sample_set_variant: bits 13, 14 of VLM_TUNE_GEMV_VARIANT, process-wide)
+int g_sample_variant = 0;
+constexpr int SV_LSE_REGS = 1 << 13, SV_TAIL_LEAN = 1 << 14;
+
+inline void launch_lse_partial(const void* logits, int ld, int B, int V, float* ws, hipStream_t st) {
+  const int per = ((V + NBLK - 1) / NBLK + 7) & ~7;
+  if ((g_sample_variant & SV_LSE_REGS) && per <= 256 * LSE_NV)
+    hipLaunchKernelGGL(lse_partial_kernel_regs, dim3(NBLK, B), dim3(256), 0, st, (const bf16_t*)logits, ld, V, ws);
+  else
+    hipLaunchKernelGGL(lse_partial_kernel, dim3(NBLK, B), dim3(256), 0, st, (const bf16_t*)logits, ld, V, ws);
+}
+
 // logprobs (bf16) + per-block argmax candidate
 __global__ __launch_bounds__(256) void logprob_argmax_kernel(const bf16_t* __restrict__ logits, int ld, int V,
                                                              const float* __restrict__ ws, bf16_t* __restrict__ logprobs,
@@ -250,10 +298,21 @@ __global__ __launch_bounds__(256) void argmax_final_advance_rows_kernel(const fl
 // token ring, step counter) and the embedding gather of the NEXT step (nn.Embedding, language.py:164,179) into h.
 // Hand-off recipe (cdna_hip_programming.md, Guideline 16): plain candidate stores -> release fence (agent) -> asm
 // vmcnt(0) -> relaxed agent fetch_add; the last arriver: acquire fence (agent) -> barrier -> plain loads.
+//
+// LEAN (VLM_TUNE_GEMV_VARIANT bit 14; logprob_argmax_tail_kernel_lean) changes when things happen, never what is computed:
+//   * the logits loads of a thread's first two vector trips (all there are at V = 151,936) go out FIRST, ahead of the loads
+//     of the 64 partials, their reduction and the expf / logf - they depend on none of that: one memory round trip for both;
+//   * one row (gridDim.y == 1): the block that takes the last row ticket IS the last block - no drain behind the re-arm and
+//     no second fetch_add on the launch's ticket (that level exists for many rows).
+// logprobs == nullptr (a generation nobody reads log-probs of): the row is neither packed nor stored, in either form; the
+// argmax over bf16(logit - lse) is unchanged.  (generate_step(return_logprobs=False) passes nullptr under the Python layer's
+// skip_logprobs switch.)  Measured in profiles/decode_tail_entry_ab.txt: LEAN is 1.0 us shorter in the trace and nothing end to end,
+// so the Python layer leaves bit 14 off.
 // ------------------------------------------------------------------------------------------
 constexpr int TAIL_MAX_B = 64;
 
-__global__ __launch_bounds__(256) void logprob_argmax_tail_kernel(
+template <bool LEAN>
+__device__ __forceinline__ void logprob_argmax_tail_body(
     const bf16_t* __restrict__ logits, int ld, int V, const float* __restrict__ ws, bf16_t* __restrict__ logprobs, int ldlp,
     float* cand_v, int* cand_i, unsigned* ticket, int* __restrict__ tok, int* __restrict__ ctx, int* __restrict__ pos,
     int* __restrict__ out_ring, int ring_len, int* __restrict__ step, const bf16_t* __restrict__ embed,
@@ -264,32 +323,49 @@ __global__ __launch_bounds__(256) void logprob_argmax_tail_kernel(
   __shared__ int s_tok[TAIL_MAX_B];
   const int b = blockIdx.y, blk = blockIdx.x, tid = threadIdx.x;
   const int li = tid & 63;
-  const float pm = ws[(size_t)b * ROW_W + li * 2], ps = ws[(size_t)b * ROW_W + li * 2 + 1];
-  const float m = wave_max(pm);
-  const float s = wave_sum(pm > -INFINITY ? ps * expf(pm - m) : 0.f);
-  const float lse = rbf(m + logf(s));          // logsumexp materialised in the logits dtype (ar.py:368)
   const int per = ((V + NBLK - 1) / NBLK + 7) & ~7;
   const int lo = blk * per, hi = min(V, lo + per);
   const bf16_t* row = logits + (size_t)b * ld;
-  float best = -INFINITY;
-  int besti = 0x7fffffff;
   // 8 elements per thread and trip where rows and pitches allow 16-byte accesses (elementwise + an order-free argmax with the
   // index tie rule: the same log-probs and candidate as the scalar loop); the ragged end of the last block stays scalar
   const bool vec = ((ld | ldlp) & 7) == 0 && (((uintptr_t)logits | (uintptr_t)logprobs) & 15) == 0;
   const int hi8 = vec ? lo + ((hi - lo) & ~7) : lo;
-  for (int i = lo + tid * 8; i < hi8; i += 256 * 8) {
-    const u32x4_t w = *reinterpret_cast<const u32x4_t*>(row + i);
-    u32x4_t o;
+  const int i0 = lo + tid * 8, i1 = i0 + 256 * 8;
+  u32x4_t w0 = {0, 0, 0, 0}, w1 = {0, 0, 0, 0};
+  if (LEAN) {
+    if (i0 < hi8) w0 = *reinterpret_cast<const u32x4_t*>(row + i0);
+    if (i1 < hi8) w1 = *reinterpret_cast<const u32x4_t*>(row + i1);
+    __builtin_amdgcn_sched_barrier(0);   // issued ahead of the partials' loads
+  }
+  const float pm = ws[(size_t)b * ROW_W + li * 2], ps = ws[(size_t)b * ROW_W + li * 2 + 1];
+  const float m = wave_max(pm);
+  const float s = wave_sum(pm > -INFINITY ? ps * expf(pm - m) : 0.f);
+  const float lse = rbf(m + logf(s));          // logsumexp materialised in the logits dtype (ar.py:368)
+  float best = -INFINITY;
+  int besti = 0x7fffffff;
+  auto trip = [&](const int i, const u32x4_t w) {
+    bf16_t l[8];
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       const bf16_t l0 = f2bf(bf_lo(w[q]) - lse), l1 = f2bf(bf_hi(w[q]) - lse);
-      o[q] = (uint32_t)l0 | ((uint32_t)l1 << 16);
+      l[2 * q] = l0;
+      l[2 * q + 1] = l1;
       const float p0 = bf2f(l0), p1 = bf2f(l1);
       if (p0 > best || (p0 == best && i + 2 * q < besti)) { best = p0; besti = i + 2 * q; }
       if (p1 > best || (p1 == best && i + 2 * q + 1 < besti)) { best = p1; besti = i + 2 * q + 1; }
     }
-    if (logprobs) *reinterpret_cast<u32x4_t*>(logprobs + (size_t)b * ldlp + i) = o;
+    if (logprobs) {
+      u32x4_t o;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) o[q] = (uint32_t)l[2 * q] | ((uint32_t)l[2 * q + 1] << 16);
+      *reinterpret_cast<u32x4_t*>(logprobs + (size_t)b * ldlp + i) = o;
+    }
+  };
+  if (LEAN) {
+    if (i0 < hi8) trip(i0, w0);
+    if (i1 < hi8) trip(i1, w1);
   }
+  for (int i = LEAN ? i1 + 256 * 8 : i0; i < hi8; i += 256 * 8) trip(i, *reinterpret_cast<const u32x4_t*>(row + i));
   for (int i = hi8 + tid; i < hi; i += 256) {
     const bf16_t lpb = f2bf(bf2f(row[i]) - lse);
     if (logprobs) logprobs[(size_t)b * ldlp + i] = lpb;
@@ -321,8 +397,12 @@ __global__ __launch_bounds__(256) void logprob_argmax_tail_kernel(
     int last = 0;
     if (__hip_atomic_fetch_add(row_ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1u) {
       __hip_atomic_store(row_ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);       // every block of the row has arrived: re-arm
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      last = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.y - 1u;
+      if (LEAN && gridDim.y == 1) {
+        last = 1;        // the only row: the launch's ticket is not touched (it stays zero; the re-arm below stores zero over it)
+      } else {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        last = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.y - 1u;
+      }
     }
     if (last) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
     s_last = last;
@@ -367,6 +447,17 @@ __global__ __launch_bounds__(256) void logprob_argmax_tail_kernel(
     __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // every block has arrived: re-arm
   }
 }
+
+#define VLM_TAIL_PARAMS                                                                                                         \
+  const bf16_t *__restrict__ logits, int ld, int V, const float *__restrict__ ws, bf16_t *__restrict__ logprobs, int ldlp,      \
+      float *cand_v, int *cand_i, unsigned *ticket, int *__restrict__ tok, int *__restrict__ ctx, int *__restrict__ pos,        \
+      int *__restrict__ out_ring, int ring_len, int *__restrict__ step, const bf16_t *__restrict__ embed,                       \
+      bf16_t *__restrict__ h, int D, int ldh, int B, VlmWindow wn
+#define VLM_TAIL_ARGS logits, ld, V, ws, logprobs, ldlp, cand_v, cand_i, ticket, tok, ctx, pos, out_ring, ring_len, step, embed, h, D, ldh, B, wn
+__global__ __launch_bounds__(256) void logprob_argmax_tail_kernel(VLM_TAIL_PARAMS) { logprob_argmax_tail_body<false>(VLM_TAIL_ARGS); }
+__global__ __launch_bounds__(256) void logprob_argmax_tail_kernel_lean(VLM_TAIL_PARAMS) { logprob_argmax_tail_body<true>(VLM_TAIL_ARGS); }
+#undef VLM_TAIL_PARAMS
+#undef VLM_TAIL_ARGS
 
 
 // ------------------------------------------------------------------------------------------
@@ -1751,7 +1842,7 @@ static int sample_ex_impl(const void* logits, int ld, int B, int V, void* logpro
   // ... and from logits: the log-prob pass runs inside the histogram launch (topp_hist_kernel<true>)
   const bool fused_lp = split && !lp_given && ld % 8 == 0 && ((uintptr_t)logits & 15) == 0;
   if (!lp_given) {
-    hipLaunchKernelGGL(lse_partial_kernel, dim3(NBLK, B), dim3(256), 0, st, (const bf16_t*)logits, ld, V, ws);
+    launch_lse_partial(logits, ld, B, V, ws, st);
     VLM_CHECK_LAUNCH(); ++t_last_launches;
     if (!fused_lp) {
       hipLaunchKernelGGL(logprob_argmax_kernel, dim3(NBLK, B), dim3(256), 0, st, (const bf16_t*)logits, ld, V, ws,
@@ -1837,7 +1928,7 @@ static int sample_rows_impl(const void* logits, int ld, int B, int V, void* logp
   const bool fused_lp = split && !lp_given && ld % 8 == 0 && ((uintptr_t)logits & 15) == 0;
   constexpr int LDS = LH_WORDS * (int)sizeof(uint32_t);
   if (!lp_given) {
-    hipLaunchKernelGGL(lse_partial_kernel, dim3(NBLK, B), dim3(256), 0, st, (const bf16_t*)logits, ld, V, ws);
+    launch_lse_partial(logits, ld, B, V, ws, st);
     VLM_CHECK_LAUNCH(); ++t_last_launches;
     if (!fused_lp) {
       hipLaunchKernelGGL(logprob_argmax_kernel, dim3(NBLK, B), dim3(256), 0, st, (const bf16_t*)logits, ld, V, ws,
@@ -1887,6 +1978,8 @@ static int sample_rows_impl(const void* logits, int ld, int B, int V, void* logp
   VLM_CHECK_LAUNCH(); ++t_last_launches;
   return VLM_OK;
 }
+
+VLM_INTERNAL void vlm_sample_set_variant(int bits) { g_sample_variant = bits; }
 
 extern "C" int vlm_sample_ex(const void* logits, int ld, int B, int V, void* logprobs, void* scratch, int ldlp, void* tok,
                              void* workspace, const vlm_sampler_params* sp, const void* step_ptr, void* stream) {
@@ -1969,11 +2062,12 @@ VLM_INTERNAL int vlm_sample_greedy_advance_win(const void* logits, int ld, int B
   float* ws = (float*)((char*)workspace + 256);
   float* cand_v = ws + ROW_CV;
   int* cand_i = (int*)(ws + ROW_CI);
-  hipLaunchKernelGGL(lse_partial_kernel, dim3(NBLK, B), dim3(256), 0, st, (const bf16_t*)logits, ld, V, ws);
+  launch_lse_partial(logits, ld, B, V, ws, st);
   VLM_CHECK_LAUNCH();
-  hipLaunchKernelGGL(logprob_argmax_tail_kernel, dim3(NBLK, B), dim3(256), 0, st, (const bf16_t*)logits, ld, V, ws,
-                     (bf16_t*)logprobs, ldlp, cand_v, cand_i, ticket, (int*)tok, (int*)ctx, (int*)pos, (int*)out_ring, ring_len,
-                     (int*)step, (const bf16_t*)embed, (bf16_t*)h, D, ldh, B, wn);
+  const auto tail = (g_sample_variant & SV_TAIL_LEAN) ? logprob_argmax_tail_kernel_lean : logprob_argmax_tail_kernel;
+  hipLaunchKernelGGL(tail, dim3(NBLK, B),
+                     dim3(256), 0, st, (const bf16_t*)logits, ld, V, ws, (bf16_t*)logprobs, ldlp, cand_v, cand_i, ticket, (int*)tok,
+                     (int*)ctx, (int*)pos, (int*)out_ring, ring_len, (int*)step, (const bf16_t*)embed, (bf16_t*)h, D, ldh, B, wn);
   VLM_CHECK_LAUNCH();
   return VLM_OK;
 }

@@ -457,6 +457,9 @@ def generate_step(input_ids, model, pixel_values, mask, *, max_tokens: int = DEF
     lookahead = max(1, min(int(lookahead), st.ring_len - 1))     # (< ring_len: no slot is rewritten before it was read)
     if host_ring is None:
         host_ring = bool(getattr(lm, "tuning", {}).get("host_ring"))
+    # nobody reads the log-prob row of a return_logprobs=False generation: the greedy tail is told not to store it (the
+    # Python-sampler and penalties routes keep it) under LanguageModel.TUNING_DEFAULTS["skip_logprobs"] / VLM_DECODE_SKIP_LOGPROBS=1
+    step_logprobs = bool(return_logprobs) or not getattr(lm, "tuning", {}).get("skip_logprobs", 0)
     win0 = seq.window_state() if st.window is not None else None
     if st.window is not None and not own_cache:
         # steps enqueued ahead of the consumer overwrite the oldest entries of a window (an unbounded cache only writes slots the
@@ -483,7 +486,8 @@ def generate_step(input_ids, model, pixel_values, mask, *, max_tokens: int = DEF
                                                    # at it (a stop token) has not advanced the matcher past the end
                     stage_mask(int(pipe.get(issued)[0]))
                 maybe_quantize_kv_cache()          # (the forward just enqueued may have carried the cache past the start)
-                lm.decode_run(st, 1, sargs, use_graph=use_graph, penalties=penalties, host_ring=host_ring)
+                lm.decode_run(st, 1, sargs, use_graph=use_graph, penalties=penalties, host_ring=host_ring,
+                              with_logprobs=step_logprobs)
                 issued += 1
                 if host_ring:      # the sampling step counter stands at `issued` when this step runs (token 0 used step 0)
                     pipe.push_host(issued, st.host_ring[issued % st.ring_len])

@@ -369,14 +369,20 @@ class LanguageModel:
         self._init_pool()
 
     # decode-step tuning (results are identical under every setting up to bf16 ties; defaults from the measurements in
-    # DESIGN.md, environment overrides VLM_DECODE_<NAME> for A/B runs).  gemv_variant 6669 = bits 0, 2, 3, 9, 11, 12 of
+    # DESIGN.md, environment overrides VLM_DECODE_<NAME> for A/B runs).  gemv_variant 14925 = 6669 | 64 | 8192; 6669 = bits 0, 2, 3, 9, 11, 12 of
     # VLM_TUNE_GEMV_VARIANT: down projection at 6 rows per workgroup, gate/up and head at 2 rows per wave
     # (profiles/decode_slack_ab.txt), the partial-only attention of a one-row step over 4 workgroups per page
     # (profiles/latency_launches_ab.txt), attention + o_proj of a one-row greedy step over as many splits as its context
     # has pages, in classes of 4 (profiles/split_classes_ab.txt) and, up to 1024 tokens, over exactly that many
-    # (profiles/split_exact_ab.txt); host_ring (tokens through a pinned ring, no copy kernel
-    # per step) measured +0.2-0.4 % in four series, under the project's bar each time: off
-    TUNING_DEFAULTS = {"fused_tail": 1, "mfma_gemv": 1, "attn_pagesplit": 16, "gemv_variant": 6669, "attn_merge": 1, "host_ring": 0}
+    # (profiles/split_exact_ab.txt).  | 64 | 8192 = bits 6 and 13 (profiles/decode_tail_entry_ab.txt): the one-row qkv launch
+    # that waits for no scalar load ahead of its weights (clears the bar alone) and the log-sum-exp partials in one pass
+    # over memory; with them host_ring (tokens through a pinned ring, no copy kernel per step) is on: each of the two is
+    # under the bar alone and positive in every series, and the step as a whole clears the bar against the parent with
+    # them (+12.6 / +13.9 tok/s).  Bit 14 (the tail's early loads and one ticket level) and skip_logprobs
+    # (generate_step(return_logprobs=False) hands its greedy steps no log-prob pointer, so the tail stores no 300 KB row
+    # nobody reads) were not positive in both series alone: off, behind their switches
+    TUNING_DEFAULTS = {"fused_tail": 1, "mfma_gemv": 1, "attn_pagesplit": 16, "gemv_variant": 6669 | 64 | 8192, "attn_merge": 1,
+                       "host_ring": 1, "skip_logprobs": 0}
 
     def apply_tuning(self, **over):
         L = _lib.lib()
@@ -917,11 +923,13 @@ class LanguageModel:
         return _lib.KvPool(pool.kpool.data_ptr(), pool.vpool.data_ptr(), pool.layer_stride, bt.data_ptr(), pool.max_pages, *q)
 
     def decode_run(self, st: DecodeState, n_steps: int, sampler_args: dict, use_graph: bool = True, penalties=None,
-                   host_ring: bool = False):
+                   host_ring: bool = False, with_logprobs: bool = True):
         """Enqueue n_steps decode steps (graph replays when use_graph).  penalties: sample_utils.LogitsProcessors, or "rows":
         the state's per-row tables (row_penalty_tables - what a token bitmask travels in).  host_ring: the steps write their
         tokens into st.host_ring (pinned; slot = sampling step % ring_len) instead of st.out_ring - the caller reads them
-        there behind an event and enqueues no copy of st.tok."""
+        there behind an event and enqueues no copy of st.tok.  with_logprobs=False: a greedy step without penalties leaves
+        st.logprobs alone (the tail gets no log-prob pointer and stores no row); sampled steps and steps with penalties
+        write the row whatever is asked."""
         L = _lib.lib()
         if st.window is None and any(s.rotating for s in st.seqs):
             raise NotImplementedError("max_kv_size: the captured step writes at slot = tokens seen; a rotating window runs "
@@ -957,11 +965,13 @@ class LanguageModel:
             n_pages = (st.seqs[0].kv_entries + n_steps + 63) // 64
             if n_pages <= 16:
                 flags |= n_pages << _lib.DECODE_NSPLITS_SHIFT
-        args = st.args(flags=flags, penalties=penalties, **sampler_args)
+        with_logprobs = bool(with_logprobs) or penalties is not None
+        args = st.args(flags=flags, penalties=penalties, with_logprobs=with_logprobs, **sampler_args)
         if os.environ.get("VLM_NO_GRAPH"):           # diagnostics: every launch of the step visible to the HIP runtime's log
             use_graph = False
         if use_graph:
-            key = (st.seq_row0, st.nsplit, fused, bool(host_ring), q8, st.window, flags & (_lib.DECODE_SPLITS_MASK | _lib.DECODE_NSPLITS_MASK),
+            key = (st.seq_row0, st.nsplit, fused, bool(host_ring), with_logprobs, q8, st.window,
+                   flags & (_lib.DECODE_SPLITS_MASK | _lib.DECODE_NSPLITS_MASK),
                    penalties if isinstance(penalties, str) else penalties.key() if penalties else None,
                    tuple(sorted(sampler_args.items())))
             if st.graph_key != key or getattr(self, "_graph_owner", None) is not st:

@@ -31,13 +31,13 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 # (label, translation unit, regex on the mangled symbol) - the launches of a one-row greedy step, in step order
 KERNELS = [
-    ("qkv       gemv_rowwave_kernel<2,3,1,1,1024>", "gemv_bf16", r"gemv_rowwave_kernelILi2ELi3ELi1ELi1ELi1024EE"),
+    ("qkv       gemv_rowwave_kernel<2,3,1,1,3072>  (bit 6, scalar entry)", "gemv_bf16", r"gemv_rowwave_kernelILi2ELi3ELi1ELi1ELi3072EE"),
     ("attention attn_decode_pagesplit_dz_kernel<6,true,4>", "attn_decode", r"attn_decode_pagesplit_dz_kernelILi6ELb1ELi4EE"),
     ("o_proj    gemv_rowwave_kernel<2,3,1,3,8>", "gemv_bf16", r"gemv_rowwave_kernelILi2ELi3ELi1ELi3ELi8EE"),
     ("gate/up   gemv_rowwave_kernel<2,3,1,1,16>", "gemv_bf16", r"gemv_rowwave_kernelILi2ELi3ELi1ELi1ELi16EE"),
     ("down      gemv_splitk_kernel<6,5,1,8>", "gemv_bf16", r"gemv_splitk_kernelILi6ELi5ELi1ELi8EE"),
     ("head      gemv_rowwave_kernel<2,3,1,1,0>", "gemv_bf16", r"gemv_rowwave_kernelILi2ELi3ELi1ELi1ELi0EE"),
-    ("lse       lse_partial_kernel", "sample", r"lse_partial_kernelE?PKt"),
+    ("lse       lse_partial_kernel_regs  (bit 13)", "sample", r"lse_partial_kernel_regsE?PKt"),
     ("tail      logprob_argmax_tail_kernel", "sample", r"logprob_argmax_tail_kernelE?PKt"),
 ]
 # the forms the attention launch takes under the other settings of bits 8, 9 of VLM_TUNE_GEMV_VARIANT; listed, not counted
@@ -49,6 +49,11 @@ ALTERNATES = [
     ("o_proj    gemv_rowwave_kernel<2,3,1,6,8>  (bit 11, 8 slots)", "gemv_bf16", r"gemv_rowwave_kernelILi2ELi3ELi1ELi6ELi8EE"),
     ("o_proj    gemv_rowwave_kernel<2,3,1,24,8>  (bit 12, 8 splits)", "gemv_bf16", r"gemv_rowwave_kernelILi2ELi3ELi1ELi24ELi8EE"),
     ("o_proj    gemv_rowwave_kernel<2,3,1,25,8>  (bit 12, 9 splits)", "gemv_bf16", r"gemv_rowwave_kernelILi2ELi3ELi1ELi25ELi8EE"),
+    # bit 6 off: the qkv entry that waits for RopeKvArgs (more than one row, wide heads); bit 13 off: the two-pass lse; bit 14:
+    # the greedy tail with its logits loads ahead of the partials'
+    ("qkv       gemv_rowwave_kernel<2,3,1,1,1024>  (bit 6 off)", "gemv_bf16", r"gemv_rowwave_kernelILi2ELi3ELi1ELi1ELi1024EE"),
+    ("lse       lse_partial_kernel  (bit 13 off)", "sample", r"lse_partial_kernelE?PKt"),
+    ("tail      logprob_argmax_tail_kernel_lean  (bit 14)", "sample", r"logprob_argmax_tail_kernel_leanE?PKt"),
 ]
 
 
