@@ -52,7 +52,9 @@ int vlm_abi_version(void);
  * Replaces nn.Linear (mlx_vlm/models/qwen2_vl/vision.py:110-120,129-130,137,161,168-173;
  * language.py:52-55,76,120; models/mlp.py:9-14), embed_tokens.as_linear / lm_head
  * (language.py:514-517) and the Conv3d patch projection (vision.py:83-101).
- * K % 8 == 0, N % 8 == 0.  With VLM_EPI_SWIGLU, C is [M, N/2]. */
+ * K % 8 == 0, N % 8 == 0.  With VLM_EPI_SWIGLU, C is [M, N/2].
+ * Added within ABI v8: VLM_EPI_BIAS | VLM_EPI_SWIGLU (the biased gate / up of qwen2_5_vl/vision.py:166-174) - bias [N]
+ * interleaved like W's rows; g = bf16(x Wg^T + bg), u = bf16(x Wu^T + bu), one rounding each, then silu(g) * u. */
 int vlm_gemm_bf16(const void* A, const void* W, const void* bias, const void* res, void* C, int M, int N, int K,
                   int lda, int ldw, int ldc, int ldres, int epilogue, void* stream);
 
@@ -216,7 +218,12 @@ int vlm_kv_gather(void* qkv, int ld, int T, int Hq, int Hkv, int D, const void* 
  * bit 2 = cu_seqlens is followed by q_start int32 [nseg]: rows of segment s before q_start[s] are KEYS ONLY (the
  * cached prefix of a prompt chunk appended to a non-empty cache, ar.py:426-472 / dispatch.py:861-882 - the causal
  * mask stays on absolute rows, i.e. offset by the cache length as base.py:366-373 builds it); their rows of `out`
- * are not written and total_qblocks = sum_s ceil((len_s - q_start_s) / 128).  Not with bit 1. */
+ * are not written and total_qblocks = sum_s ceil((len_s - q_start_s) / 128).  Not with bit 1.
+ * Added within ABI v8: bit 3 = the ONE-TILE form (csrc/attn_window.hip; the window blocks of the Qwen2.5-VL tower,
+ * qwen2_5_vl/vision.py:149-163): every segment has 1..64 tokens, so its K and V are one tile and the softmax is a single exact
+ * pass; two (segment, head) pairs per workgroup.  `total_qblocks` then carries the caller's DECLARED longest segment.
+ * VLM_ERR_SHAPE with nothing enqueued when D != 80, Hq != Hkv or that maximum exceeds 64; not with bits 0 / 2 (VLM_ERR_ARG);
+ * bit 1 is accepted and has no effect.  Of a segment longer than declared only the first 64 tokens are read and written. */
 int vlm_attn_prefill(const void* q, const void* k, const void* v, void* out, int q_stride, int k_stride, int v_stride,
                      int o_stride, const void* cu_seqlens, int nseg, int total_qblocks, int Hq, int Hkv, int D,
                      float scale, int causal, void* stream);
@@ -738,8 +745,12 @@ typedef struct vlm_vit_config {
   float ln_eps;
   int qk_interleaved; /* 1: the q / k rows of every wqkv / bqkv are interleaved per head (vlm_gemm_bf16_rope2d) and
                          cos_tab / sin_tab of vlm_vit_args are ONE table (sin_tab == cos_tab + N * head_dim / 2): the 2-D
-                         rope runs in the qkv GEMM epilogue instead of a pass of its own */
+                         rope runs in the qkv GEMM epilogue instead of a pass of its own.
+                         Added within ABI v8: the field is a FLAG WORD.  Bit 0 keeps that meaning; bit 1
+                         (VLM_VIT_FORM_QWEN2_5) selects the Qwen2.5-VL block form, see vlm_vit_forward below */
 } vlm_vit_config;
+#define VLM_VIT_QK_INTERLEAVED 1
+#define VLM_VIT_FORM_QWEN2_5 2
 
 typedef struct vlm_vit_block {
   const void *ln1_w, *ln1_b, *wqkv, *bqkv, *wproj, *bproj, *ln2_w, *ln2_b, *wfc1, *bfc1, *wfc2, *bfc2;
@@ -750,7 +761,19 @@ typedef struct vlm_vit_globals {
 } vlm_vit_globals;
 
 /* VisionModel.__call__ (vision.py:257-290): patches bf16 [N][patch_k] -> out bf16 [N/merge^2][out_dim].
- * Workspaces: x [N][E], xn [N][E], qkv [N][3E], attn [N][E], mlp [N][mlp_hidden], mrg [N/4][4E]. */
+ * Workspaces: x [N][E], xn [N][E], qkv [N][3E], attn [N][E], mlp [N][mlp_hidden], mrg [N/4][4E].
+ *
+ * Added within ABI v8 - the Qwen2.5-VL form (VLM_VIT_FORM_QWEN2_5 | VLM_VIT_QK_INTERLEAVED in vlm_vit_config.qk_interleaved;
+ * reference mlx_vlm/models/qwen2_5_vl/vision.py:177-193,326-393).  Per block: RMSNorm, qkv GEMM + bias with the 2-D rope in
+ * its epilogue, attention over the window table (or over cu_seqlens for a block of fullatt_mask), proj GEMM + bias +
+ * residual, RMSNorm, gate / up GEMM + bias + SwiGLU, down GEMM + bias + residual; merger RMSNorm -> [N/4][4E] -> Linear +
+ * GELU(erf) -> Linear.  vlm_vit_block keeps its 12 pointers: ln1_b == ln2_b == NULL, wfc1 / bfc1 = the gate / up rows and
+ * biases INTERLEAVED (gate_j, up_j) as VLM_EPI_SWIGLU wants them, [2 mlp_hidden][E] / [2 mlp_hidden], wfc2 / bfc2 = down
+ * [E][mlp_hidden]; mlp_hidden = intermediate_size zero-padded to a multiple of 64 (a padded unit gives silu(0) * 0 = 0);
+ * vlm_vit_globals.ln_q_b == NULL.  The rows are taken in WINDOW order: behind the patch GEMM the N / merge^2 merge units
+ * are gathered by window_index (cos_tab / sin_tab are passed in that order already), behind the merger the rows are gathered
+ * back by reverse_index - both on the device, inside the call.  Workspaces as above; head_dim % 16 == 0,
+ * out_dim <= merge^2 * mlp_hidden (the un-permuted merger rows borrow the mlp workspace). */
 typedef struct vlm_vit_args {
   const void* patches;
   int N;
@@ -759,6 +782,18 @@ typedef struct vlm_vit_args {
   int nseg, total_qblocks;
   void *x, *xn, *qkv, *attn, *mlp, *mrg, *out;
   int uniform_segments;          /* 1: all segments have the same length (vlm_attn_prefill placement hint) */
+  /* Added within ABI v8, APPENDED: read only for a handle created with VLM_VIT_FORM_QWEN2_5 - a caller of the first form may
+   * keep passing the struct up to uniform_segments.  The window table of the tower's window blocks (vision.py:261-346),
+   * int32 [win_nseg + 1] over the rows in WINDOW order, zero-length windows dropped; win_total_qblocks as total_qblocks;
+   * win_max_seg = its longest segment; win_one_tile != 0: window blocks run the one-tile attention (vlm_attn_prefill bit 3;
+   * needs win_max_seg <= 64 and head_dim 80), 0: the general kernel over the same table.  window_index / reverse_index int32
+   * [N / merge^2]: row u of the window order is merge unit window_index[u] of the patch rows, and output row j is row
+   * reverse_index[j] = argsort(window_index)[j] of the merger's.  fullatt_mask: bit i set = block i attends over cu_seqlens
+   * (fullatt_block_indexes; depth <= 64). */
+  const void* win_cu_seqlens;
+  int win_nseg, win_total_qblocks, win_max_seg, win_one_tile;
+  const void *window_index, *reverse_index;
+  unsigned long long fullatt_mask;
 } vlm_vit_args;
 
 int vlm_vit_create(const vlm_vit_config* cfg, void** handle);

@@ -96,8 +96,16 @@ class VitArgs(C.Structure):
     _fields_ = [("patches", c_void_p), ("N", c_int), ("cos_tab", c_void_p), ("sin_tab", c_void_p),
                 ("cu_seqlens", c_void_p), ("nseg", c_int), ("total_qblocks", c_int), ("x", c_void_p), ("xn", c_void_p),
                 ("qkv", c_void_p), ("attn", c_void_p), ("mlp", c_void_p), ("mrg", c_void_p), ("out", c_void_p),
-                ("uniform_segments", c_int)]
+                ("uniform_segments", c_int),
+                # appended within ABI v8, read only for a VIT_FORM_QWEN2_5 handle (zero for every other caller)
+                ("win_cu_seqlens", c_void_p), ("win_nseg", c_int), ("win_total_qblocks", c_int), ("win_max_seg", c_int),
+                ("win_one_tile", c_int), ("window_index", c_void_p), ("reverse_index", c_void_p),
+                ("fullatt_mask", C.c_ulonglong)]
 
+
+VIT_QK_INTERLEAVED = 1                      # vlm_vit_config.qk_interleaved, a flag word: bit 0 = rope in the qkv GEMM epilogue
+VIT_FORM_QWEN2_5 = 2                        # bit 1 = the Qwen2.5-VL block form (RMSNorm, biased SwiGLU, window attention)
+ATTN_PREFILL_ONE_TILE = 8                   # vlm_attn_prefill's flag word, bit 3: the one-tile form (csrc/attn_window.hip)
 
 class ImagePatchArgs(C.Structure):
     """vlm_image_patch_args (include/vlm_hip.h): what vlm_cast_f32_bf16_pad reads through `src` when ld_src == CAST_PAD_IMAGE_MODE"""

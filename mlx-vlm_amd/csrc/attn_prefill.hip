@@ -30,6 +30,7 @@
 #include <stdlib.h>
 
 #include "common.hpp"
+#include "internal.h"
 #include "../../include/vlm_hip.h"
 
 #ifdef ATTN_STAMPS
@@ -379,6 +380,13 @@ extern "C" int vlm_attn_prefill(const void* q, const void* k, const void* v, voi
                                 int Hkv, int D, float scale, int causal, void* stream) {
   if (!q || !k || !v || !out || !cu_seqlens || nseg <= 0 || Hq <= 0 || Hkv <= 0 || Hq % Hkv != 0) return VLM_ERR_ARG;
   if (q_stride % 8 || k_stride % 8 || v_stride % 8 || o_stride % 4) return VLM_ERR_SHAPE;
+  // bit 3: the one-tile form (csrc/attn_window.hip) - every segment fits one 64-key tile, `total_qblocks` is the caller's
+  // declared longest segment.  No mask, no key-only prefix; the placement hint (bit 1) has nothing to place.
+  if (causal & 8) {
+    if (causal & 5) return VLM_ERR_ARG;
+    return vlm_attn_window(q, k, v, out, q_stride, k_stride, v_stride, o_stride, cu_seqlens, nseg, total_qblocks, Hq, Hkv, D, scale,
+                           stream);
+  }
   if (total_qblocks <= 0) return VLM_OK;
   hipStream_t st = (hipStream_t)stream;
   const float sl2 = scale * 1.44269504088896340736f;

@@ -712,9 +712,57 @@ extern "C" int vlm_vit_set_globals(void* handle, const vlm_vit_globals* g) {
   return 0;
 }
 
+// The Qwen2.5-VL form of the tower (VLM_VIT_FORM_QWEN2_5; reference qwen2_5_vl/vision.py:177-193,326-393): RMSNorm blocks with a
+// biased SwiGLU MLP, window attention in all but the fullatt blocks, the rows in window order between two device gathers.
+static int vit_forward_qwen2_5(const Vit* v, const vlm_vit_args* a, void* stream) {
+  const vlm_vit_config& c = v->cfg;
+  const int E = c.embed_dim, H = c.n_heads, hd = E / H, N = a->N, MH = c.mlp_hidden;
+  const int mm = c.merge * c.merge;
+  if (N % mm != 0 || hd % 16 != 0 || c.depth > 64 || (long)c.out_dim > (long)mm * MH) return 2;
+  if (!(c.qk_interleaved & VLM_VIT_QK_INTERLEAVED) ||
+      a->sin_tab != off(const_cast<void*>(a->cos_tab), (size_t)N * (hd / 2) * sizeof(float)))
+    return 1;                             // this form has the rope in the qkv GEMM epilogue only
+  if (!a->win_cu_seqlens || !a->window_index || !a->reverse_index || !a->cu_seqlens || a->win_nseg <= 0) return 1;
+  const bool one_tile = a->win_one_tile != 0;
+  if (one_tile && (a->win_max_seg > 64 || hd != 80)) return 2;
+  const float scale = 1.0f / sqrtf((float)hd);
+  const int Nm = N / mm, EM = E * mm;
+  // patch projection into the attn workspace, then the merge units into window order (hidden_states[window_index], 349-353)
+  TRY(vlm_gemm_bf16(a->patches, v->g.wpatch, nullptr, nullptr, a->attn, N, E, c.patch_k, c.patch_k, c.patch_k, E, 0, VLM_EPI_NONE, stream));
+  TRY(vlm_embed_gather(a->window_index, a->attn, a->x, Nm, EM, EM, Nm, stream));
+  for (int i = 0; i < c.depth; ++i) {
+    const vlm_vit_block& w = v->blocks[i];
+    const bool full = (a->fullatt_mask >> i) & 1ull;
+    TRY(vlm_rmsnorm_residual(a->x, nullptr, w.ln1_w, a->xn, nullptr, N, E, c.ln_eps, stream));
+    TRY(vlm_gemm_bf16_rope2d(a->xn, w.wqkv, w.bqkv, a->cos_tab, a->qkv, N, 3 * E, E, E, E, 3 * E, hd, 2 * E, stream));
+    void* kq = off(a->qkv, (size_t)E * 2);
+    void* vq = off(a->qkv, (size_t)2 * E * 2);
+    if (full)
+      TRY(vlm_attn_prefill(a->qkv, kq, vq, a->attn, 3 * E, 3 * E, 3 * E, E, a->cu_seqlens, a->nseg, a->total_qblocks, H, H, hd, scale,
+                           a->uniform_segments ? 2 : 0, stream));
+    else if (one_tile)
+      TRY(vlm_attn_prefill(a->qkv, kq, vq, a->attn, 3 * E, 3 * E, 3 * E, E, a->win_cu_seqlens, a->win_nseg, a->win_max_seg, H, H, hd,
+                           scale, 8, stream));
+    else
+      TRY(vlm_attn_prefill(a->qkv, kq, vq, a->attn, 3 * E, 3 * E, 3 * E, E, a->win_cu_seqlens, a->win_nseg, a->win_total_qblocks, H, H,
+                           hd, scale, 0, stream));
+    TRY(vlm_gemm_bf16(a->attn, w.wproj, w.bproj, a->x, a->x, N, E, E, E, E, E, E, VLM_EPI_BIAS | VLM_EPI_RESIDUAL, stream));
+    TRY(vlm_rmsnorm_residual(a->x, nullptr, w.ln2_w, a->xn, nullptr, N, E, c.ln_eps, stream));
+    TRY(vlm_gemm_bf16(a->xn, w.wfc1, w.bfc1, nullptr, a->mlp, N, 2 * MH, E, E, E, MH, 0, VLM_EPI_BIAS | VLM_EPI_SWIGLU, stream));
+    TRY(vlm_gemm_bf16(a->mlp, w.wfc2, w.bfc2, a->x, a->x, N, E, MH, MH, MH, E, E, VLM_EPI_BIAS | VLM_EPI_RESIDUAL, stream));
+  }
+  // PatchMerger: RMSNorm -> [N/4, 4E] -> Linear + GELU(erf) -> Linear, then back out of window order (391-392)
+  TRY(vlm_rmsnorm_residual(a->x, nullptr, v->g.ln_q_w, a->xn, nullptr, N, E, c.ln_eps, stream));
+  TRY(vlm_gemm_bf16(a->xn, v->g.wm0, v->g.bm0, nullptr, a->mrg, Nm, EM, EM, EM, EM, EM, 0, VLM_EPI_BIAS | VLM_EPI_GELU_ERF, stream));
+  TRY(vlm_gemm_bf16(a->mrg, v->g.wm2, v->g.bm2, nullptr, a->mlp, Nm, c.out_dim, EM, EM, EM, c.out_dim, 0, VLM_EPI_BIAS, stream));
+  TRY(vlm_embed_gather(a->reverse_index, a->mlp, a->out, Nm, c.out_dim, c.out_dim, Nm, stream));
+  return 0;
+}
+
 extern "C" int vlm_vit_forward(void* handle, const vlm_vit_args* a, void* stream) {
   Vit* v = static_cast<Vit*>(handle);
   if (!v || !a || !a->patches || a->N <= 0) return 1;
+  if (v->cfg.qk_interleaved & VLM_VIT_FORM_QWEN2_5) return vit_forward_qwen2_5(v, a, stream);
   const vlm_vit_config& c = v->cfg;
   const int E = c.embed_dim, H = c.n_heads, hd = E / H, N = a->N, MH = c.mlp_hidden;
   const int mm = c.merge * c.merge;

@@ -831,6 +831,9 @@ __attribute__((visibility("hidden"))) int vlm_gemm256_try(const void* A, const v
     case VLM_EPI_SWIGLU:
       if (N % 16 != 0) return -1;
       return launch256<VLM_EPI_SWIGLU>(A, W, bias, res, C, M, N, K, lda, ldw, ldc, ldres, st);
+    case VLM_EPI_BIAS | VLM_EPI_SWIGLU:      // biased gate / up (the Qwen2.5-VL tower's MLP): bias interleaved like the rows
+      if (N % 16 != 0) return -1;
+      return launch256<VLM_EPI_BIAS | VLM_EPI_SWIGLU>(A, W, bias, res, C, M, N, K, lda, ldw, ldc, ldres, st);
     default: return -1;
   }
 }

@@ -907,6 +907,7 @@ static int gemm_dispatch(const void* A, const void* W, const void* bias, const v
     case VLM_EPI_BIAS | VLM_EPI_RESIDUAL: GO(VLM_EPI_BIAS | VLM_EPI_RESIDUAL);
     case VLM_EPI_RESIDUAL: GO(VLM_EPI_RESIDUAL);
     case VLM_EPI_SWIGLU: GO(VLM_EPI_SWIGLU);
+    case VLM_EPI_BIAS | VLM_EPI_SWIGLU: GO(VLM_EPI_BIAS | VLM_EPI_SWIGLU);      // bias interleaved like the (gate, up) rows
     default: return VLM_ERR_ARG;
   }
 #undef GO

@@ -17,6 +17,12 @@ VLM_INTERNAL int vlm_attn_prefill_paged_bf16(const void* q, int ldq, void* out, 
                                              const void* q_start, int nseg, int total_qblocks, int Hq, int Hkv, float scale,
                                              void* stream);
 
+// one-tile form of vlm_attn_prefill (csrc/attn_window.hip): what the exported entry does with bit 3 of its flag word.  Segments of
+// 1 .. 64 tokens, D == 80, Hq == Hkv, max_seg = the caller's declared longest segment (VLM_ERR_SHAPE otherwise, nothing enqueued)
+VLM_INTERNAL int vlm_attn_window(const void* q, const void* k, const void* v, void* out, int q_stride, int k_stride, int v_stride,
+                                 int o_stride, const void* cu_seqlens, int nseg, int max_seg, int Hq, int Hkv, int D, float scale,
+                                 void* stream);
+
 // ---- skinny-M decode GEMM on the matrix cores (csrc/gemv_mfma.hip): 3 <= M <= 16 batch rows
 struct VlmRopeKv {
   const int* pos;            // [M] rope position (all three M-RoPE axes are equal for a decoded text token)

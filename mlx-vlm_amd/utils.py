@@ -22,7 +22,7 @@ import torch
 # model_type aliases of the reference (utils.py:34-62): the checkpoint's `model_type` -> package under models/.  The
 # whole alias table is kept so that a lookup resolves exactly as it does there; families that are not built here then
 # fail in get_model_and_args with the reference's own "Model type ... not supported." (utils.py:633-635).
-# Built: qwen2_vl, llava_bunny (nanoLLaVA ships `model_type: "llava-qwen2"`, Bunny `"bunny-llama"`).
+# Built: qwen2_vl, qwen2_5_vl, phi3_v, idefics2, llava_bunny (nanoLLaVA ships `model_type: "llava-qwen2"`, Bunny `"bunny-llama"`).
 MODEL_REMAPPING: Dict[str, str] = {
     "llava-qwen2": "llava_bunny", "bunny-llama": "llava_bunny", "llava_qwen2": "fastvlm", "lfm2-vl": "lfm2_vl",
     "cohere2_vision": "aya_vision", "jvlm": "jina_vlm", "phi4-siglip": "phi4_siglip", "sam3_video": "sam3",
@@ -245,7 +245,13 @@ def load_processor(model_path: str, config, image_preprocess: str = "host"):
                 ip_kwargs[k] = pc[k]
     if image_preprocess == "device":
         ip_kwargs["device"] = "cuda"
-    proc = Qwen2VLProcessor(Qwen2VLImageProcessor(**ip_kwargs), tok)
+    if MODEL_REMAPPING.get(mt, mt) == "qwen2_5_vl":
+        # reference qwen2_5_vl/processing_qwen2_5_vl.py: the Qwen2-VL image processor (patch 14) + mm_token_type_ids on request
+        from .models.qwen2_5_vl.processing_qwen2_5_vl import Qwen2_5_VLProcessor
+
+        proc = Qwen2_5_VLProcessor(Qwen2VLImageProcessor(**ip_kwargs), tok)
+    else:
+        proc = Qwen2VLProcessor(Qwen2VLImageProcessor(**ip_kwargs), tok)
     eos = config.eos_token_id if getattr(config, "eos_token_id", None) is not None else tok.eos_token_id
     tok.stopping_criteria = StoppingCriteria(eos if isinstance(eos, list) else [eos], tok)
     proc.detokenizer = _pick_detokenizer(model_path, tok)
