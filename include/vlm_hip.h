@@ -45,6 +45,10 @@ extern "C" {
  * A shape the flagged kernel does not take is refused (return 2) and nothing is enqueued. */
 #define VLM_EPI_X_TILED 64
 #define VLM_EPI_Y_TILED 128
+/* vlm_gemm_bf16 only, added within ABI v8 (bit 5 is taken inside the library): nn.GELU(approx="tanh"),
+ * 0.5 x (1 + tanh(sqrt(2/pi) (x + 0.044715 x^3))) on the bf16-rounded acc + bias, every elementary op rounded to bf16 as
+ * the two GELU forms above (qwen3_vl/vision.py:169).  Every tile, staging and split-K form that takes VLM_EPI_GELU_FAST. */
+#define VLM_EPI_GELU_TANH 256
 
 int vlm_abi_version(void);
 
@@ -196,6 +200,11 @@ int vlm_mrope_kvwrite(void* qkv, int ld, int T, int Hq, int Hkv, int D, const vo
 /* the same with SuScaledRoPE's input scale (rope_utils.py:174-176, Phi-3.5 phi3_v.py:41-48): q and k are multiplied by
  * qk_scale and rounded to bf16 (the reference's typed `scale.astype(x.dtype) * x`) before the rotation; v is not scaled.
  * qk_scale = 1 is vlm_mrope_kvwrite bit for bit. */
+/* sec0 < 0 (added within ABI v8): the QK-NORM form of Qwen3-VL (qwen3_vl/language.py:84-89, selector rope_utils.py:511-516).
+ * mrope_section = (-sec0, sec1, D / 2 + sec0 - sec1) under the INTERLEAVED selector, and inv_freq points at ONE fp32 table
+ * [D / 2 inv_freq | eps | D q_norm_w | D k_norm_w].  Per (row, q or k head): y = T(w * T(x * rsqrt(mean(x^2) + eps))) - the
+ * roundings of vlm_rmsnorm_residual - then the fp32 rotation of y and one rounding; q back in place, rotated k and the
+ * untouched v into the pools.  D == 128 (VLM_ERR_SHAPE otherwise), qk_scale == 1 (VLM_ERR_ARG otherwise). */
 int vlm_mrope_kvwrite_scaled(void* qkv, int ld, int T, int Hq, int Hkv, int D, const void* pos_t, const void* pos_h,
                              const void* pos_w, const void* inv_freq, int sec0, int sec1, const void* kv_seq,
                              const void* kv_slot, const void* block_table, int max_pages, void* kpool, void* vpool,
@@ -315,6 +324,8 @@ int vlm_gemv_attn_out_bf16(const void* part_o, const void* part_ml, int nsplit, 
 int vlm_embed_gather(const void* ids, const void* table, void* out, int T, int D, int ldo, int vocab, void* stream);
 
 /* Model.merge_input_ids_with_image_features (qwen2_vl.py:78-148): dst[dst_rows[i]] = src[i] */
+/* n < 0 (added within ABI v8): the ADD form over -n rows, dst[dst_rows[i]] = T(dst[dst_rows[i]] + src[i]) - DeepStack's
+ * h[visual rows] += deepstack_visual_embeds[layer] (qwen3_vl/language.py:231-283); the rows must be distinct */
 int vlm_scatter_image_rows(const void* src, const void* dst_rows, void* dst, int n, int D, int ld_src, int ld_dst,
                            void* stream);
 
@@ -510,6 +521,10 @@ typedef struct vlm_llm_layer {
   /* MLX affine 4-bit layers (vlm_gemv_w4): a non-NULL *_sb marks the matching w* as q words uint32 [N][K/8] with *_sb its
    * (scale | bias << 16) words uint32 [N][K/64]; NULL = bf16 weight as before.  Rows packed / interleaved the same way. */
   const void *wqkv_sb, *wo_sb, *wgu_sb, *wdown_sb;
+  /* Added within ABI v8, APPENDED: read only by a handle in VLM_MODE_QWEN3 (set BEFORE vlm_llm_set_layer, which otherwise copies
+   * the struct up to wdown_sb - a caller of the earlier form may keep passing it that long).  q_norm / k_norm of Qwen3's
+   * attention (qwen3_vl/language.py:84-89): fp32 [head_dim] each, the checkpoint's weights widened (exact); bqkv is NULL there */
+  const void *q_norm_w, *k_norm_w;
 } vlm_llm_layer;
 
 typedef struct vlm_llm_globals {
@@ -566,6 +581,13 @@ typedef struct vlm_prefill_args {
   void *xlast, *logits;
   int rope_long; /* models with rope_long_from > 0: 1 = this call uses the LONG frequency table (the caller applies
                     SuScaledRoPE's per-call rule: max cache offset + tokens of the call > original_max) */
+  /* Added within ABI v8, APPENDED: read only by a handle in VLM_MODE_QWEN3 - a caller of the earlier form may keep passing the
+   * struct up to rope_long.  DeepStack (qwen3_vl/language.py:231-283): after decoder layer i < n_ds, h[ds_rows[j]] +=
+   * ds_embeds[i][j] (one typed bf16 add per element) for j < n_ds_rows.  ds_embeds bf16 [n_ds][n_ds_rows][hidden], ds_rows int32
+   * [n_ds_rows], distinct rows of h (the image-token rows of THIS call: a chunked prefill passes the slice of its chunk).
+   * ds_embeds == NULL or n_ds_rows == 0: none */
+  const void *ds_embeds, *ds_rows;
+  int n_ds, n_ds_rows;
 } vlm_prefill_args;
 
 /* one decode step for B sequences (B in {1,2,4,8}); every buffer is device resident so the
@@ -722,6 +744,15 @@ int vlm_llm_decode_launches(void* handle);
 #define VLM_MODE_WINDOW_RING_POS 18 /* 1: the rope position follows the ring's write index (the reference's Qwen2-VL reads
                                        cache._idx as its offset, qwen2_vl/language.py:426-431); 0 (default): it follows the tokens
                                        seen (cache.offset: the plain-rope families) */
+#define VLM_MODE_QWEN3 19           /* 1: the Qwen3-VL language model (added within ABI v8; set right after vlm_llm_create, BEFORE
+                                       vlm_llm_set_layer; head_dim == 128, one rope table, no rope_qk_scale - argument error
+                                       otherwise).  Every q and k head goes through RMSNorm(head_dim) with vlm_llm_layer.q_norm_w /
+                                       k_norm_w and rms_eps between the qkv projection and the rotation, and the rotation takes the
+                                       INTERLEAVED selector over mrope_section (rope_utils.py:511-516: frequency f reads the h position
+                                       when f % 3 == 1 and f < 3 sec1, the w position when f % 3 == 2 and f < 3 sec2, else t).  The qkv
+                                       step of a decode layer is then TWO launches at every row count - the projection with its
+                                       RMSNorm prologue, then the QK-norm form of the rotary + KV-write launch - and vlm_llm_prefill
+                                       reads the DeepStack fields of vlm_prefill_args.  0 (default): everything as before */
 int vlm_llm_set_tuning(void* handle, int key, int value);
 int vlm_llm_get_tuning(void* handle, int key);
 
@@ -747,17 +778,25 @@ typedef struct vlm_vit_config {
                          cos_tab / sin_tab of vlm_vit_args are ONE table (sin_tab == cos_tab + N * head_dim / 2): the 2-D
                          rope runs in the qkv GEMM epilogue instead of a pass of its own.
                          Added within ABI v8: the field is a FLAG WORD.  Bit 0 keeps that meaning; bit 1
-                         (VLM_VIT_FORM_QWEN2_5) selects the Qwen2.5-VL block form, see vlm_vit_forward below */
+                         (VLM_VIT_FORM_QWEN2_5) selects the Qwen2.5-VL block form, bit 2 (VLM_VIT_FORM_QWEN3) the Qwen3-VL
+                         form, see vlm_vit_forward below */
 } vlm_vit_config;
 #define VLM_VIT_QK_INTERLEAVED 1
 #define VLM_VIT_FORM_QWEN2_5 2
+#define VLM_VIT_FORM_QWEN3 4
 
 typedef struct vlm_vit_block {
   const void *ln1_w, *ln1_b, *wqkv, *bqkv, *wproj, *bproj, *ln2_w, *ln2_b, *wfc1, *bfc1, *wfc2, *bfc2;
+  /* Added within ABI v8, APPENDED: read only for a handle created with VLM_VIT_FORM_QWEN3 (vlm_vit_set_block copies the first
+   * 12 pointers otherwise).  tap_w0 != NULL: a DeepStack tap follows this block - the post-shuffle PatchMerger of
+   * deepstack_merger_list (qwen3_vl/vision.py:106-123): LayerNorm weights / bias [4E], Linear [4E][4E] + bias, Linear
+   * [out_dim][4E] + bias.  The taps fill vlm_vit_args.tap_out in block order. */
+  const void *tap_ln_w, *tap_ln_b, *tap_w0, *tap_b0, *tap_w2, *tap_b2;
 } vlm_vit_block;
 
 typedef struct vlm_vit_globals {
   const void *wpatch /* [embed_dim][patch_k] */, *ln_q_w, *ln_q_b, *wm0, *bm0, *wm2, *bm2;
+  const void* bpatch; /* added within ABI v8, APPENDED, VLM_VIT_FORM_QWEN3 handles only: the patch Conv3d's bias, bf16 [embed_dim] */
 } vlm_vit_globals;
 
 /* VisionModel.__call__ (vision.py:257-290): patches bf16 [N][patch_k] -> out bf16 [N/merge^2][out_dim].
@@ -794,6 +833,17 @@ typedef struct vlm_vit_args {
   int win_nseg, win_total_qblocks, win_max_seg, win_one_tile;
   const void *window_index, *reverse_index;
   unsigned long long fullatt_mask;
+  /* Added within ABI v8, APPENDED: read only for a handle created with VLM_VIT_FORM_QWEN3 | VLM_VIT_QK_INTERLEAVED (reference
+   * mlx_vlm/models/qwen3_vl/vision.py:379-425).  That form is the FIRST form's block (LayerNorm, biased qkv with the 2-D rope
+   * in the GEMM epilogue, attention over cu_seqlens, biased MLP) with: x = T(T(patches Wp^T + bpatch) + pos_rows) in front -
+   * pos_rows bf16 [N][embed_dim] = fast_pos_embed_interpolate's rows, in the patch rows' merge-unit order (made by the caller);
+   * VLM_EPI_GELU_TANH in the MLP; behind every block whose vlm_vit_block.tap_w0 is set, the post-shuffle merger of that block
+   * into tap_out bf16 [n_taps][N / merge^2][out_dim] (n_taps = the number of such blocks, VLM_ERR_ARG otherwise); then the main
+   * merger of the first form.  head_dim in {64, 80, 128}, merge^2 * embed_dim <= 8192 (VLM_ERR_SHAPE otherwise).  The window
+   * fields above are not read. */
+  const void* pos_rows;
+  void* tap_out;
+  int n_taps;
 } vlm_vit_args;
 
 int vlm_vit_create(const vlm_vit_config* cfg, void** handle);

@@ -23,7 +23,9 @@ class LlmConfig(C.Structure):
 
 class LlmLayer(C.Structure):
     _fields_ = [(n, c_void_p) for n in ("ln1_w", "wqkv", "bqkv", "wo", "ln2_w", "wgu", "wdown",
-                                        "wqkv_sb", "wo_sb", "wgu_sb", "wdown_sb")]
+                                        "wqkv_sb", "wo_sb", "wgu_sb", "wdown_sb",
+                                        # appended within ABI v8, read only by a handle in MODE_QWEN3: fp32 [head_dim] each
+                                        "q_norm_w", "k_norm_w")]
 
 
 class LlmGlobals(C.Structure):
@@ -40,7 +42,9 @@ class PrefillArgs(C.Structure):
     _fields_ = [("h", c_void_p), ("T", c_int), ("pos_t", c_void_p), ("pos_h", c_void_p), ("pos_w", c_void_p),
                 ("kv_seq", c_void_p), ("kv_slot", c_void_p), ("cu_seqlens", c_void_p), ("nseg", c_int),
                 ("total_qblocks", c_int), ("xn", c_void_p), ("qkv", c_void_p), ("attn", c_void_p), ("act", c_void_p),
-                ("last_rows", c_void_p), ("n_last", c_int), ("xlast", c_void_p), ("logits", c_void_p), ("rope_long", c_int)]
+                ("last_rows", c_void_p), ("n_last", c_int), ("xlast", c_void_p), ("logits", c_void_p), ("rope_long", c_int),
+                # appended within ABI v8, read only by a handle in MODE_QWEN3 (DeepStack; zero for every other caller)
+                ("ds_embeds", c_void_p), ("ds_rows", c_void_p), ("n_ds", c_int), ("n_ds_rows", c_int)]
 
 
 class EncLayer(C.Structure):
@@ -85,11 +89,15 @@ class VitConfig(C.Structure):
 
 class VitBlock(C.Structure):
     _fields_ = [(n, c_void_p) for n in ("ln1_w", "ln1_b", "wqkv", "bqkv", "wproj", "bproj", "ln2_w", "ln2_b", "wfc1",
-                                        "bfc1", "wfc2", "bfc2")]
+                                        "bfc1", "wfc2", "bfc2",
+                                        # appended within ABI v8, read only for a VIT_FORM_QWEN3 handle: the DeepStack tap
+                                        # merger behind this block (tap_w0 NULL: none)
+                                        "tap_ln_w", "tap_ln_b", "tap_w0", "tap_b0", "tap_w2", "tap_b2")]
 
 
 class VitGlobals(C.Structure):
-    _fields_ = [(n, c_void_p) for n in ("wpatch", "ln_q_w", "ln_q_b", "wm0", "bm0", "wm2", "bm2")]
+    _fields_ = [(n, c_void_p) for n in ("wpatch", "ln_q_w", "ln_q_b", "wm0", "bm0", "wm2", "bm2",
+                                        "bpatch")]      # appended within ABI v8, VIT_FORM_QWEN3 handles only
 
 
 class VitArgs(C.Structure):
@@ -100,11 +108,14 @@ class VitArgs(C.Structure):
                 # appended within ABI v8, read only for a VIT_FORM_QWEN2_5 handle (zero for every other caller)
                 ("win_cu_seqlens", c_void_p), ("win_nseg", c_int), ("win_total_qblocks", c_int), ("win_max_seg", c_int),
                 ("win_one_tile", c_int), ("window_index", c_void_p), ("reverse_index", c_void_p),
-                ("fullatt_mask", C.c_ulonglong)]
+                ("fullatt_mask", C.c_ulonglong),
+                # appended within ABI v8, read only for a VIT_FORM_QWEN3 handle
+                ("pos_rows", c_void_p), ("tap_out", c_void_p), ("n_taps", c_int)]
 
 
 VIT_QK_INTERLEAVED = 1                      # vlm_vit_config.qk_interleaved, a flag word: bit 0 = rope in the qkv GEMM epilogue
 VIT_FORM_QWEN2_5 = 2                        # bit 1 = the Qwen2.5-VL block form (RMSNorm, biased SwiGLU, window attention)
+VIT_FORM_QWEN3 = 4                          # bit 2 = the Qwen3-VL form (patch bias + position rows, tanh-GELU, DeepStack taps)
 ATTN_PREFILL_ONE_TILE = 8                   # vlm_attn_prefill's flag word, bit 3: the one-tile form (csrc/attn_window.hip)
 
 class ImagePatchArgs(C.Structure):
@@ -128,6 +139,7 @@ DECODE_ROW_SAMPLER = 1 << 11                # the tail samples in row-table mode
 TUNE_MFMA_GEMV, TUNE_ATTN_PAGESPLIT, TUNE_GEMV_VARIANT, TUNE_ATTN_MERGE = 6, 7, 8, 9  # vlm_llm_set_tuning keys (include/vlm_hip.h)
 # modes of the decode step (same entry point, but these DO change what a DECODE_WINDOW step computes)
 MODE_WINDOW_SIZE, MODE_WINDOW_KEEP, MODE_WINDOW_RING_POS = 16, 17, 18
+MODE_QWEN3 = 19                             # 1: QK-norm + interleaved M-RoPE + DeepStack (set before vlm_llm_set_layer)
 
 P = C.POINTER
 # name -> (restype, argtypes); every symbol include/vlm_hip.h declares

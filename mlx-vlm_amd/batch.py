@@ -335,13 +335,14 @@ class BatchGenerator:
         grid_l = [b[3].get("image_grid_thw") for b in batch]
         extras = [{k: v for k, v in b[3].items() if k not in ("pixel_values", "image_grid_thw", _PROCS_KEY, _PYPROCS_KEY, _BUDGET_KEY, _MASKPROC_KEY, _SAMPLER_KEY)}
                   for b in batch]
-        emb, pos, lens, deltas = embed_requests(self.model, ids_l, pix_l, grid_l, extras)
+        ds = []                   # Qwen3-VL: the DeepStack rows of all requests, concatenated like their prompts
+        emb, pos, lens, deltas = embed_requests(self.model, ids_l, pix_l, grid_l, extras, deepstack_out=ds)
         caches = []
         try:
             for L, b in zip(lens, batch):
                 caches.append(lm.make_cache())
                 caches[-1][0]._seq.reserve(L + b[2] + 2)          # prompt + every token it may generate + the step in flight
-            logits = lm.prefill(emb, pos, caches, lens, "last")
+            logits = lm.prefill(emb, pos, caches, lens, "last", **({"deepstack": ds[0]} if ds else {}))
         except BaseException:
             self._release_caches(caches)             # (no sequence slot or page stays with a failed admission)
             raise
@@ -487,6 +488,9 @@ class BatchGenerator:
             raise NotImplementedError("BatchGenerator(apc_manager=): automatic prefix caching is built for the Qwen2-VL family; "
                                       f"{type(model).__module__} embeds its prompts through its own get_input_embeddings")
         lm = model.language_model
+        if getattr(lm, "DEEPSTACK", False):
+            raise NotImplementedError("BatchGenerator(apc_manager=): a warm admission skips the vision tower, and the DeepStack "
+                                      "features of Qwen3-VL's image rows are not cached")
         if getattr(lm, "head_dim", 128) != 128:
             raise NotImplementedError("BatchGenerator(apc_manager=): the paged prefill attention is built for 128-wide heads")
 

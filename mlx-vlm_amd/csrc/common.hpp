@@ -164,6 +164,19 @@ __device__ __forceinline__ float gelu_erf_(float x) {
   const float o = rbf(1.0f + rbf(erff(t)));
   return 0.5f * rbf(x * o);
 }
+// nn.GELU(approx="tanh") : 0.5 x (1 + tanh(sqrt(2/pi) (x + 0.044715 x^3)))   (reference qwen3_vl/vision.py:169)
+// Typed graph: 0.5 * x -> T (exact), x ** 3 -> T (the fp32 product of three bf16 values is exact), T(0.044715) = 0.044677734375
+// times it -> T, x + . -> T, T(sqrt(2 / pi)) = 0.796875 times it -> T, tanh -> T, 1 + . -> T, product (rounded by the caller).
+// tanh(d) = 1 - 2 / (1 + e^(2 d)) on v_exp_f32 + v_rcp_f32: absolute error ~1e-7, and the value only enters T(1 + T(tanh)),
+// whose spacing is 2^-8 or wider; e^(2 d) = inf / 0 give the limits +1 / -1.
+__device__ __forceinline__ float gelu_tanh_(float x) {
+  const float a = 0.5f * x;
+  const float x3 = rbf(x * x * x);
+  const float c = rbf(x + rbf(0.044677734375f * x3));
+  const float d = rbf(0.796875f * c);
+  const float th = 1.0f - 2.0f * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(2.88539008177792681472f * d));
+  return a * rbf(1.0f + rbf(th));
+}
 // swiglu typed graph: sig -> T, g*sig -> T, *u -> T      (reference activations.py:7-9)
 __device__ __forceinline__ float swiglu_(float g, float u) {
   float sig = rbf(sigmoidf_(g));

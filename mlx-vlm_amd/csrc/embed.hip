@@ -5,6 +5,8 @@
 //                         (reference mlx_vlm/models/qwen2_vl/qwen2_vl.py:78-148): the cumsum /
 //                         gather / where there collapses to "row dst_rows[i] of the embeddings :=
 //                         image feature row i" once the image-token positions are known on the host
+//                         n < 0: the add form, dst[dst_rows[i]] += src[i] over -n rows (DeepStack,
+//                         qwen3_vl/language.py:231-283)
 // vlm_cast_f32_bf16_pad   pixel_values.astype(weight dtype) (qwen2_vl.py:44-45) fused with the
 //                         zero padding of K = 1176 -> 1216 the patch GEMM wants; ld_src == -1: the rows are made from
 //                         a raw u8 image on the device instead (image_preprocess.hip)
@@ -35,6 +37,24 @@ __global__ __launch_bounds__(256) void scatter_rows_kernel(const bf16_t* __restr
   if (idx >= (long)n * cpr) return;
   const int r = (int)(idx / cpr), c = (int)(idx % cpr);
   reinterpret_cast<uint4*>(dst + (size_t)dst_rows[r] * ldd)[c] = reinterpret_cast<const uint4*>(src + (size_t)r * lds_)[c];
+}
+
+// DeepStack (reference mlx_vlm/models/qwen3_vl/language.py:231-283 _deepstack_process): dst[rows[i]] = T(dst[rows[i]] + src[i]),
+// one typed bf16 add per element; the rows are distinct, so no two threads meet
+__global__ __launch_bounds__(256) void add_rows_kernel(const bf16_t* __restrict__ src, const int* __restrict__ dst_rows,
+                                                       bf16_t* __restrict__ dst, int n, int D, int lds_, int ldd) {
+  const int cpr = D >> 3;
+  const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= (long)n * cpr) return;
+  const int r = (int)(idx / cpr), c = (int)(idx % cpr);
+  uint4* d = reinterpret_cast<uint4*>(dst + (size_t)dst_rows[r] * ldd) + c;
+  const uint4 a = *d, b = reinterpret_cast<const uint4*>(src + (size_t)r * lds_)[c];
+  uint4 o;
+  o.x = pack_bf2(bf_lo(a.x) + bf_lo(b.x), bf_hi(a.x) + bf_hi(b.x));
+  o.y = pack_bf2(bf_lo(a.y) + bf_lo(b.y), bf_hi(a.y) + bf_hi(b.y));
+  o.z = pack_bf2(bf_lo(a.z) + bf_lo(b.z), bf_hi(a.z) + bf_hi(b.z));
+  o.w = pack_bf2(bf_lo(a.w) + bf_lo(b.w), bf_hi(a.w) + bf_hi(b.w));
+  *d = o;
 }
 
 __global__ __launch_bounds__(256) void cast_pad_kernel(const float* __restrict__ src, bf16_t* __restrict__ dst, int rows,
@@ -82,11 +102,23 @@ extern "C" int vlm_embed_gather(const void* ids, const void* table, void* out, i
 
 extern "C" int vlm_scatter_image_rows(const void* src, const void* dst_rows, void* dst, int n, int D, int ld_src,
                                       int ld_dst, void* stream) {
-  if (!src || !dst_rows || !dst || n < 0 || D <= 0) return VLM_ERR_ARG;
+  if (n < 0) return vlm_add_rows(src, dst_rows, dst, -n, D, ld_src, ld_dst, stream);      // the add form (DeepStack)
+  if (!src || !dst_rows || !dst || D <= 0) return VLM_ERR_ARG;
   if (D % 8 || ld_src % 8 || ld_dst % 8) return VLM_ERR_SHAPE;
   if (n == 0) return VLM_OK;
   const long total = (long)n * (D / 8);
   hipLaunchKernelGGL(scatter_rows_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                     (const bf16_t*)src, (const int*)dst_rows, (bf16_t*)dst, n, D, ld_src, ld_dst);
+  VLM_CHECK_LAUNCH();
+  return VLM_OK;
+}
+
+VLM_INTERNAL int vlm_add_rows(const void* src, const void* dst_rows, void* dst, int n, int D, int ld_src, int ld_dst, void* stream) {
+  if (!src || !dst_rows || !dst || n < 0 || D <= 0) return VLM_ERR_ARG;
+  if (D % 8 || ld_src % 8 || ld_dst % 8) return VLM_ERR_SHAPE;
+  if (n == 0) return VLM_OK;
+  const long total = (long)n * (D / 8);
+  hipLaunchKernelGGL(add_rows_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                      (const bf16_t*)src, (const int*)dst_rows, (bf16_t*)dst, n, D, ld_src, ld_dst);
   VLM_CHECK_LAUNCH();
   return VLM_OK;

@@ -12,7 +12,9 @@
 // enqueues the whole chain on a HIP stream with no host work in between.
 #include <hip/hip_runtime.h>
 
+#include <stddef.h>
 #include <stdlib.h>
+#include <string.h>
 
 #include <new>
 #include <vector>
@@ -51,6 +53,8 @@ struct Tuning {
   int attn_merge = 1;                     // 1: one-row steps merge the page-split partials in the o_proj prologue
   // modes of the decode step (VLM_MODE_*): unlike the knobs above these change what a VLM_DECODE_WINDOW step computes
   int win_size = 0, win_keep = 0, win_ring_pos = 0;
+  // VLM_MODE_QWEN3: per-head RMSNorm between the qkv projection and the (interleaved) rotation, DeepStack adds in the prefill
+  int qwen3 = 0;
 };
 
 struct Llm {
@@ -174,6 +178,7 @@ extern "C" int vlm_llm_set_tuning(void* handle, int key, int value) {
     case VLM_MODE_WINDOW_SIZE: if (value < 0) return 1; slot = &m->tune.win_size; break;
     case VLM_MODE_WINDOW_KEEP: if (value < 0) return 1; slot = &m->tune.win_keep; break;
     case VLM_MODE_WINDOW_RING_POS: if (value < 0 || value > 1) return 1; slot = &m->tune.win_ring_pos; break;
+    case VLM_MODE_QWEN3: if (value < 0 || value > 1 || (value && m->cfg.head_dim != 128)) return 1; slot = &m->tune.qwen3; break;
     default: return 1;
   }
   if (key == VLM_TUNE_GEMV_VARIANT) {
@@ -200,6 +205,7 @@ extern "C" int vlm_llm_get_tuning(void* handle, int key) {
     case VLM_MODE_WINDOW_SIZE: return m->tune.win_size;
     case VLM_MODE_WINDOW_KEEP: return m->tune.win_keep;
     case VLM_MODE_WINDOW_RING_POS: return m->tune.win_ring_pos;
+    case VLM_MODE_QWEN3: return m->tune.qwen3;
     default: return -1;
   }
 }
@@ -207,7 +213,14 @@ extern "C" int vlm_llm_get_tuning(void* handle, int key) {
 extern "C" int vlm_llm_set_layer(void* handle, int layer, const vlm_llm_layer* w) {
   Llm* m = static_cast<Llm*>(handle);
   if (!m || !w || layer < 0 || layer >= m->cfg.n_layers) return 1;
-  m->layers[layer] = *w;
+  // a caller that never set VLM_MODE_QWEN3 passes the struct as it was before the mode: nothing behind wdown_sb is read
+  if (m->tune.qwen3) {
+    if (!w->q_norm_w || !w->k_norm_w) return 1;
+    m->layers[layer] = *w;
+  } else {
+    m->layers[layer] = vlm_llm_layer{};
+    memcpy(&m->layers[layer], w, offsetof(vlm_llm_layer, q_norm_w));
+  }
   return 0;
 }
 
@@ -321,12 +334,17 @@ extern "C" int vlm_llm_prefill(void* handle, const vlm_prefill_args* a, void* st
   const float scale = c.attn_scale > 0.f ? c.attn_scale : 1.0f / sqrtf((float)hd);
   const float qk_scale = c.rope_qk_scale > 0.f ? c.rope_qk_scale : 1.f;
   bool xn_ready = false;      // xn already holds RMSNorm(h) of the coming layer (the previous down GEMM's split-K reduce launch wrote it)
+  // VLM_MODE_QWEN3 (the fields behind rope_long are read in this mode only): DeepStack - after decoder layer i < n_ds the rows
+  // ds_rows of h get ds_embeds[i] added (qwen3_vl/language.py:231-283)
+  const bool q3 = m->tune.qwen3 != 0;
+  const int n_ds = q3 && a->ds_embeds && a->n_ds_rows > 0 ? a->n_ds : 0;
+  if (n_ds < 0 || n_ds > c.n_layers || (n_ds > 0 && !a->ds_rows)) return 1;
   for (int i = 0; i < c.n_layers; ++i) {
     const vlm_llm_layer& w = m->layers[i];
     // xn = RMSNorm(h)
     if (!xn_ready) TRY(vlm_rmsnorm_residual(a->h, nullptr, w.ln1_w, a->xn, nullptr, T, D, c.rms_eps, stream));
     // qkv = xn Wqkv^T + b
-    TRY(lin_gemm(m, a->xn, w.wqkv, w.wqkv_sb, w.bqkv, nullptr, a->qkv, T, QKV, D, QKV, 0, VLM_EPI_BIAS, stream));
+    TRY(lin_gemm(m, a->xn, w.wqkv, w.wqkv_sb, w.bqkv, nullptr, a->qkv, T, QKV, D, QKV, 0, w.bqkv ? VLM_EPI_BIAS : VLM_EPI_NONE, stream));
     // M-RoPE on q, k in place + paged KV write
     void* kp = m->kv.kpool ? off(m->kv.kpool, (size_t)i * m->kv.layer_stride * 2) : nullptr;
     void* vp = m->kv.vpool ? off(m->kv.vpool, (size_t)i * m->kv.layer_stride * 2) : nullptr;
@@ -334,9 +352,16 @@ extern "C" int vlm_llm_prefill(void* handle, const vlm_prefill_args* a, void* st
     // the call > original_max); the long table sits behind the short one
     const void* inv_freq = (a->rope_long && c.rope_long_from > 0) ? off(const_cast<void*>(m->g.inv_freq), (size_t)(hd / 2) * sizeof(float))
                                                                 : m->g.inv_freq;
-    TRY(vlm_mrope_kvwrite_scaled(a->qkv, QKV, T, Hq, Hkv, hd, a->pos_t, a->pos_h, a->pos_w, inv_freq, c.mrope_sec0,
-                                 c.mrope_sec1, a->kv_seq, a->kv_slot, m->kv.block_table, m->kv.max_pages, kp, vp, qk_scale,
-                                 stream));
+    if (q3) {      // per-head RMSNorm, interleaved selector, rotation, KV write (csrc/rope.hip)
+      if (kp && !m->kv.block_table) return 1;
+      TRY(vlm_mrope_qknorm_kvwrite(a->qkv, QKV, T, Hq, Hkv, hd, a->pos_t, a->pos_h, a->pos_w, inv_freq, c.mrope_sec0, c.mrope_sec1,
+                                   1, w.q_norm_w, w.k_norm_w, c.rms_eps, a->kv_seq, a->kv_slot, m->kv.block_table,
+                                   m->kv.max_pages, kp, vp, stream));
+    } else {
+      TRY(vlm_mrope_kvwrite_scaled(a->qkv, QKV, T, Hq, Hkv, hd, a->pos_t, a->pos_h, a->pos_w, inv_freq, c.mrope_sec0,
+                                   c.mrope_sec1, a->kv_seq, a->kv_slot, m->kv.block_table, m->kv.max_pages, kp, vp, qk_scale,
+                                   stream));
+    }
     // causal flash attention over each sequence
     TRY(vlm_attn_prefill(a->qkv, off(a->qkv, (size_t)Hq * hd * 2), off(a->qkv, (size_t)(Hq + Hkv) * hd * 2), a->attn, QKV,
                          QKV, QKV, Hq * hd, a->cu_seqlens, a->nseg, a->total_qblocks, Hq, Hkv, hd, scale, 1, stream));
@@ -348,7 +373,7 @@ extern "C" int vlm_llm_prefill(void* handle, const vlm_prefill_args* a, void* st
     // (round 6) a split-K down GEMM's reduce launch also writes the NEXT layer's RMSNorm(h) (VlmGemmTail: the wide decode steps'
     // mechanism, same bits as the separate launch; the last layer's rows go through the gather below instead)
     int done = 0;
-    if (i + 1 < c.n_layers) {
+    if (i + 1 < c.n_layers && i >= n_ds) {      // (a DeepStack layer changes h behind the GEMM: its successor's norm is a launch)
       VlmGemmTail nt{};
       nt.kind = VLM_TAIL_RMSNORM;
       nt.norm_w = m->layers[i + 1].ln1_w; nt.eps = c.rms_eps; nt.xn = a->xn; nt.ldxn = D;
@@ -357,6 +382,9 @@ extern "C" int vlm_llm_prefill(void* handle, const vlm_prefill_args* a, void* st
       TRY(lin_gemm(m, a->act, w.wdown, w.wdown_sb, nullptr, a->h, a->h, T, D, c.inter, D, D, VLM_EPI_RESIDUAL, stream));
     }
     xn_ready = done != 0;
+    if (i < n_ds)
+      TRY(vlm_add_rows(off(const_cast<void*>(a->ds_embeds), (size_t)i * a->n_ds_rows * D * 2), a->ds_rows, a->h, a->n_ds_rows, D, D, D,
+                       stream));
   }
   if (a->n_last > 0) {
     if (!a->last_rows || !a->xlast || !a->logits) return 1;
@@ -395,6 +423,7 @@ static int decode_impl(Llm* m, const vlm_decode_args* a, void* stream, int* laun
   // the step's tail advances all four by the window rule (internal.h vlm_window_advance).  Not over the 8-bit pools (the
   // reference: "RotatingKVCache Quantization NYI"), not with two rope tables (that epilogue reads the slot as the cache offset)
   const VlmWindow wn = window_of(tn, a->flags);
+  if (tn.qwen3 && (c.rope_long_from > 0 || (c.rope_qk_scale > 0.f && c.rope_qk_scale != 1.f))) return 1;   // (no SuScaledRoPE form)
   if (a->flags & VLM_DECODE_WINDOW) {
     if (wn.M <= wn.K + 1 || m->kv.kpool8 || c.rope_long_from > 0) return 1;
     if (B != 1 && B != 2 && B != 4 && B != 8) return 1;
@@ -428,7 +457,21 @@ static int decode_impl(Llm* m, const vlm_decode_args* a, void* stream, int* laun
     void* kp = off(m->kv.kpool, (size_t)i * m->kv.layer_stride * 2);
     void* vp = off(m->kv.vpool, (size_t)i * m->kv.layer_stride * 2);
     // [RMSNorm + qkv GEMV + bias + M-RoPE at pos[b] + k/v write at slot ctx[b]] in one launch
-    if (wide) {
+    if (tn.qwen3) {
+      // VLM_MODE_QWEN3: the per-head RMSNorm needs a whole head between the projection and the rotation, which no fused qkv
+      // launcher (a wave owns a rotation pair) and no split-K tail expresses - every row count runs the projection and then the
+      // QK-norm form of the rotary + KV-write launch (Qwen3-VL)
+      const int epi = w.bqkv ? VLM_EPI_BIAS : VLM_EPI_NONE;
+      if (wide) {
+        if (!xn_ready) { TRY(vlm_rmsnorm_residual(a->h, nullptr, w.ln1_w, xn, nullptr, B, D, c.rms_eps, stream)); ++n; }
+        TRY(lin_gemm(m, xn, w.wqkv, w.wqkv_sb, w.bqkv, nullptr, a->qkv, B, QKV, D, QKV, 0, epi, stream)); ++n;
+      } else {
+        TRY(lin_gemv(m, a->h, w.wqkv, w.wqkv_sb, w.bqkv, nullptr, w.ln1_w, a->qkv, B, QKV, D, QKV, 0, c.rms_eps, epi, xn_rows, &n, stream)); ++n;
+      }
+      TRY(vlm_mrope_qknorm_kvwrite(a->qkv, QKV, B, Hq, Hkv, hd, a->pos, a->pos, a->pos, m->g.inv_freq, c.mrope_sec0, c.mrope_sec1, 1,
+                                   w.q_norm_w, w.k_norm_w, c.rms_eps, nullptr, slot, m->kv.block_table, m->kv.max_pages, kp, vp,
+                                   stream)); ++n;
+    } else if (wide) {
       // (round 6) the three small GEMMs of a wide layer are split-K: their reduce launches also do the launch that would read
       // the reduced rows straight back - M-RoPE + KV write here, RMSNorm(ln2) after o_proj, the NEXT layer's RMSNorm(ln1) (or
       // the final norm) after down.  Same values (csrc/gemm_bf16.hip); a GEMM that does not take the split-K route reports
@@ -701,14 +744,71 @@ extern "C" int vlm_vit_destroy(void* handle) {
 extern "C" int vlm_vit_set_block(void* handle, int i, const vlm_vit_block* w) {
   Vit* v = static_cast<Vit*>(handle);
   if (!v || !w || i < 0 || i >= v->cfg.depth) return 1;
-  v->blocks[i] = *w;
+  // only a VLM_VIT_FORM_QWEN3 handle reads what was appended to the structs for it
+  if (v->cfg.qk_interleaved & VLM_VIT_FORM_QWEN3) {
+    v->blocks[i] = *w;
+  } else {
+    v->blocks[i] = vlm_vit_block{};
+    memcpy(&v->blocks[i], w, offsetof(vlm_vit_block, tap_ln_w));
+  }
   return 0;
 }
 
 extern "C" int vlm_vit_set_globals(void* handle, const vlm_vit_globals* g) {
   Vit* v = static_cast<Vit*>(handle);
   if (!v || !g) return 1;
-  v->g = *g;
+  if (v->cfg.qk_interleaved & VLM_VIT_FORM_QWEN3) {
+    v->g = *g;
+  } else {
+    v->g = vlm_vit_globals{};
+    memcpy(&v->g, g, offsetof(vlm_vit_globals, bpatch));
+  }
+  return 0;
+}
+
+// The Qwen3-VL form of the tower (VLM_VIT_FORM_QWEN3; reference qwen3_vl/vision.py:106-123,164-191,379-425): the first form's
+// LayerNorm block with a tanh-GELU MLP, a biased patch projection with the interpolated position rows added behind it, and a
+// post-shuffle PatchMerger (LayerNorm over the 2 x 2 merge unit's 4E values) behind every DeepStack tap block.
+static int vit_forward_qwen3(const Vit* v, const vlm_vit_args* a, void* stream) {
+  const vlm_vit_config& c = v->cfg;
+  const int E = c.embed_dim, H = c.n_heads, hd = E / H, N = a->N, MH = c.mlp_hidden;
+  const int mm = c.merge * c.merge;
+  if (N % mm != 0 || (hd != 64 && hd != 80 && hd != 128) || (long)E * mm > 8192) return 2;      // (rope2d epilogue, attention, LayerNorm)
+  if (!(c.qk_interleaved & VLM_VIT_QK_INTERLEAVED) ||
+      a->sin_tab != off(const_cast<void*>(a->cos_tab), (size_t)N * (hd / 2) * sizeof(float)))
+    return 1;                             // this form has the rope in the qkv GEMM epilogue only
+  if (!a->cu_seqlens || !a->pos_rows || !v->g.bpatch) return 1;
+  int n_taps = 0;
+  for (const vlm_vit_block& w : v->blocks) n_taps += w.tap_w0 != nullptr;
+  if (n_taps != a->n_taps || (n_taps > 0 && !a->tap_out)) return 1;
+  const float scale = 1.0f / sqrtf((float)hd);
+  const int Nm = N / mm, EM = E * mm;
+  // x = T(T(patches Wp^T + b) + pos_rows): the reference's two typed ops (vision.py:386-388) are the epilogue's two roundings
+  TRY(vlm_gemm_bf16(a->patches, v->g.wpatch, v->g.bpatch, a->pos_rows, a->x, N, E, c.patch_k, c.patch_k, c.patch_k, E, E,
+                    VLM_EPI_BIAS | VLM_EPI_RESIDUAL, stream));
+  int tap = 0;
+  for (int i = 0; i < c.depth; ++i) {
+    const vlm_vit_block& w = v->blocks[i];
+    TRY(vlm_layernorm(a->x, w.ln1_w, w.ln1_b, a->xn, N, E, c.ln_eps, stream));
+    TRY(vlm_gemm_bf16_rope2d(a->xn, w.wqkv, w.bqkv, a->cos_tab, a->qkv, N, 3 * E, E, E, E, 3 * E, hd, 2 * E, stream));
+    TRY(vlm_attn_prefill(a->qkv, off(a->qkv, (size_t)E * 2), off(a->qkv, (size_t)2 * E * 2), a->attn, 3 * E, 3 * E, 3 * E, E,
+                         a->cu_seqlens, a->nseg, a->total_qblocks, H, H, hd, scale, a->uniform_segments ? 2 : 0, stream));
+    TRY(vlm_gemm_bf16(a->attn, w.wproj, w.bproj, a->x, a->x, N, E, E, E, E, E, E, VLM_EPI_BIAS | VLM_EPI_RESIDUAL, stream));
+    TRY(vlm_layernorm(a->x, w.ln2_w, w.ln2_b, a->xn, N, E, c.ln_eps, stream));
+    TRY(vlm_gemm_bf16(a->xn, w.wfc1, w.bfc1, nullptr, a->mlp, N, MH, E, E, E, MH, 0, VLM_EPI_BIAS | VLM_EPI_GELU_TANH, stream));
+    TRY(vlm_gemm_bf16(a->mlp, w.wfc2, w.bfc2, a->x, a->x, N, E, MH, MH, MH, E, E, VLM_EPI_BIAS | VLM_EPI_RESIDUAL, stream));
+    if (w.tap_w0) {
+      // DeepStack tap: LayerNorm over [N/4][4E] (post-shuffle), Linear + GELU(erf), Linear -> tap_out[tap]
+      TRY(vlm_layernorm(a->x, w.tap_ln_w, w.tap_ln_b, a->xn, Nm, EM, c.ln_eps, stream));
+      TRY(vlm_gemm_bf16(a->xn, w.tap_w0, w.tap_b0, nullptr, a->mrg, Nm, EM, EM, EM, EM, EM, 0, VLM_EPI_BIAS | VLM_EPI_GELU_ERF, stream));
+      TRY(vlm_gemm_bf16(a->mrg, w.tap_w2, w.tap_b2, nullptr, off(a->tap_out, (size_t)tap * Nm * c.out_dim * 2), Nm, c.out_dim, EM, EM,
+                        EM, c.out_dim, 0, VLM_EPI_BIAS, stream));
+      ++tap;
+    }
+  }
+  TRY(vlm_layernorm(a->x, v->g.ln_q_w, v->g.ln_q_b, a->xn, N, E, c.ln_eps, stream));
+  TRY(vlm_gemm_bf16(a->xn, v->g.wm0, v->g.bm0, nullptr, a->mrg, Nm, EM, EM, EM, EM, EM, 0, VLM_EPI_BIAS | VLM_EPI_GELU_ERF, stream));
+  TRY(vlm_gemm_bf16(a->mrg, v->g.wm2, v->g.bm2, nullptr, a->out, Nm, c.out_dim, EM, EM, EM, c.out_dim, 0, VLM_EPI_BIAS, stream));
   return 0;
 }
 
@@ -762,7 +862,9 @@ static int vit_forward_qwen2_5(const Vit* v, const vlm_vit_args* a, void* stream
 extern "C" int vlm_vit_forward(void* handle, const vlm_vit_args* a, void* stream) {
   Vit* v = static_cast<Vit*>(handle);
   if (!v || !a || !a->patches || a->N <= 0) return 1;
+  if ((v->cfg.qk_interleaved & VLM_VIT_FORM_QWEN2_5) && (v->cfg.qk_interleaved & VLM_VIT_FORM_QWEN3)) return 1;
   if (v->cfg.qk_interleaved & VLM_VIT_FORM_QWEN2_5) return vit_forward_qwen2_5(v, a, stream);
+  if (v->cfg.qk_interleaved & VLM_VIT_FORM_QWEN3) return vit_forward_qwen3(v, a, stream);
   const vlm_vit_config& c = v->cfg;
   const int E = c.embed_dim, H = c.n_heads, hd = E / H, N = a->N, MH = c.mlp_hidden;
   const int mm = c.merge * c.merge;

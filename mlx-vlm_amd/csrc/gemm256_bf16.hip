@@ -112,6 +112,10 @@ __device__ __forceinline__ void epilogue256(f32x4_t (&acc)[8][NF], char* smem, c
 #pragma unroll
         for (int r = 0; r < 4; ++r) v[r] = gelu_erf_(rbf(v[r]));
       }
+      if (EPI & VLM_EPI_GELU_TANH) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) v[r] = gelu_tanh_(rbf(v[r]));
+      }
       uint2 o;
       o.x = pack_bf2(v[0], v[1]);
       o.y = pack_bf2(v[2], v[3]);
@@ -534,6 +538,10 @@ __global__ __launch_bounds__(512) void gemm256p_kernel(const bf16_t* __restrict_
 #pragma unroll
           for (int r = 0; r < 4; ++r) v[r] = gelu_erf_(rbf(v[r]));
         }
+        if (EPI & VLM_EPI_GELU_TANH) {
+#pragma unroll
+          for (int r = 0; r < 4; ++r) v[r] = gelu_tanh_(rbf(v[r]));
+        }
         uint2 o;
         o.x = pack_bf2(v[0], v[1]);
         o.y = pack_bf2(v[2], v[3]);
@@ -825,6 +833,8 @@ __attribute__((visibility("hidden"))) int vlm_gemm256_try(const void* A, const v
       return launch256<VLM_EPI_BIAS | VLM_EPI_GELU_FAST>(A, W, bias, res, C, M, N, K, lda, ldw, ldc, ldres, st);
     case VLM_EPI_BIAS | VLM_EPI_GELU_ERF:
       return launch256<VLM_EPI_BIAS | VLM_EPI_GELU_ERF>(A, W, bias, res, C, M, N, K, lda, ldw, ldc, ldres, st);
+    case VLM_EPI_BIAS | VLM_EPI_GELU_TANH:
+      return launch256<VLM_EPI_BIAS | VLM_EPI_GELU_TANH>(A, W, bias, res, C, M, N, K, lda, ldw, ldc, ldres, st);
     case VLM_EPI_BIAS | VLM_EPI_RESIDUAL:
       return launch256<VLM_EPI_BIAS | VLM_EPI_RESIDUAL>(A, W, bias, res, C, M, N, K, lda, ldw, ldc, ldres, st);
     case VLM_EPI_RESIDUAL: return launch256<VLM_EPI_RESIDUAL>(A, W, bias, res, C, M, N, K, lda, ldw, ldc, ldres, st);

@@ -10,6 +10,17 @@ VLM_INTERNAL int vlm_mrope_kvwrite_decode(void* qkv, int ld, int B, int Hq, int 
                                           int sec0, int sec1, const void* slot, const void* block_table, int max_pages,
                                           void* kpool, void* vpool, float qk_scale, int long_from, void* stream);
 
+// QK-norm form of both (csrc/rope.hip; Qwen3-VL, qwen3_vl/language.py:84-89): per q / k head RMSNorm(head_dim) with q_norm_w /
+// k_norm_w (fp32 [D]: the checkpoint's weights widened) and eps, then the rotation and the KV write; D == 128 (VLM_ERR_SHAPE
+// otherwise).  interleaved != 0: the interleaved selector over mrope_section (sec0, sec1, D / 2 - sec0 - sec1).  T token rows with
+// positions pos_t / pos_h / pos_w (a decode step passes its pos three times and kv_seq == NULL); block_table == NULL with pools:
+// the identity layout.  The exported vlm_mrope_kvwrite_scaled reaches it with a negative mrope_sec0.
+VLM_INTERNAL int vlm_mrope_qknorm_kvwrite(void* qkv, int ld, int T, int Hq, int Hkv, int D, const void* pos_t, const void* pos_h,
+                                          const void* pos_w, const void* inv_freq, int sec0, int sec1, int interleaved,
+                                          const void* q_norm_w, const void* k_norm_w, float eps, const void* kv_seq,
+                                          const void* kv_slot, const void* block_table, int max_pages, void* kpool, void* vpool,
+                                          void* stream);
+
 // bf16 form of vlm_attn_prefill_paged_q8 (csrc/attn_prefill_paged.hip): a prompt chunk attending over the bf16 pages; the
 // arguments are checked by the exported entry (csrc/attn_prefill_q8.hip), which takes this form when ksb == vsb == NULL
 VLM_INTERNAL int vlm_attn_prefill_paged_bf16(const void* q, int ldq, void* out, int ldo, const void* kpool, const void* vpool,
@@ -116,6 +127,8 @@ __device__ __forceinline__ void vlm_window_advance(int* ctx, int* pos, int B, in
 /* embed.hip: vlm_decode_advance under the window rule */
 VLM_INTERNAL int vlm_decode_advance_win(void* ctx, void* pos, const void* tok, void* out_ring, int ring_len, void* step, int B,
                                         VlmWindow wn, void* stream);
+/* embed.hip: what vlm_scatter_image_rows does with n < 0 - dst[dst_rows[i]] = T(dst[dst_rows[i]] + src[i]), distinct rows */
+VLM_INTERNAL int vlm_add_rows(const void* src, const void* dst_rows, void* dst, int n, int D, int ld_src, int ld_dst, void* stream);
 /* sample.hip: vlm_sample_greedy_advance under the window rule */
 VLM_INTERNAL int vlm_sample_greedy_advance_win(const void* logits, int ld, int B, int V, void* logprobs, int ldlp, void* tok,
                                                void* workspace, void* ctx, void* pos, void* out_ring, int ring_len, void* step,

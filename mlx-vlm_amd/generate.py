@@ -26,6 +26,7 @@ import torch
 
 from . import _lib, image_ops, ops
 from .models import cache as cache_mod
+from .models.base import deepstack_window
 from .sample_utils import Sampler, make_sampler
 
 DEFAULT_MAX_TOKENS = 2048          # reference generate/common.py:19-24
@@ -388,16 +389,24 @@ def generate_step(input_ids, model, pixel_values, mask, *, max_tokens: int = DEF
     if step_size == DEFAULT_PREFILL_STEP_SIZE and L <= ONE_SHOT_PREFILL_TOKENS:
         step_size = None
     done = 0
+
+    def deepstack(start, n):
+        """Qwen3-VL: the DeepStack rows and embeds of the prompt columns [start, start + n) (None for every other family)"""
+        ds = deepstack_window(getattr(f, "visual_pos_masks", None), getattr(f, "deepstack_visual_embeds", None), start, n)
+        return {} if ds is None else {"deepstack": ds}
+
     if step_size is not None and step_size > 0 and L > step_size and not prompt_cache[0]._seq.rotating:
         while L - done > 1:
             n = min(step_size, L - done - 1)
-            lm.prefill(E[done:done + n], P[:, done:done + n], [prompt_cache], [n], "last", reserve_extra=L - done - n + max_tokens + 2)
+            lm.prefill(E[done:done + n], P[:, done:done + n], [prompt_cache], [n], "last", reserve_extra=L - done - n + max_tokens + 2,
+                       **deepstack(done, n))
             # (the reference quantises between chunks, common.py:170-181; here the cache turns 8-bit AFTER the last prefill call:
             #  the chunk path attends over the bf16 pages - LanguageModel._prefill_onto_cache - and the whole-prompt path always
             #  quantised behind the prefill.  The chunks after quantized_kv_start so see unrounded K / V: a deviation of the
             #  PROMPT pass only, the decode steps attend over the same 8-bit pools either way)
             done += n
-    logits = lm.prefill(E[done:], P[:, done:], [prompt_cache], [L - done], "last", reserve_extra=max_tokens + 2)
+    logits = lm.prefill(E[done:], P[:, done:], [prompt_cache], [L - done], "last", reserve_extra=max_tokens + 2,
+                        **deepstack(done, L - done))
 
     if eager and mask_proc is not None:          # (a Python sampler, a thinking budget, a host-planned window: a callable again)
         mask_proc, py_procs = None, [mask_proc]
@@ -759,10 +768,11 @@ def generate(model, processor, prompt: Optional[str] = None, image=None, audio=N
 
 
 # ---------------------------------------------------------------------------------------------
-def _embed_requests_per_model(model, input_ids_list, pixel_values_list, extras):
+def _embed_requests_per_model(model, input_ids_list, pixel_values_list, extras, deepstack_out=None):
     """Model families other than Qwen2-VL (llava_bunny, phi3_v): every request through the model's own
     `get_input_embeddings` (its tower, projector and splice rule), the results concatenated for one varlen prefill."""
     embs, poss, lens, deltas = [], [], [], []
+    ds_embeds, ds_rows, row0 = [], [], 0
     # one tower pass for the images of ALL requests where the model offers it (`encode_images_batched`: per-request features,
     # computed together - the GEMMs of 4 x 729 rows of one request run at a fraction of the rate of 32 x 729)
     feats = None
@@ -782,14 +792,30 @@ def _embed_requests_per_model(model, input_ids_list, pixel_values_list, extras):
         poss.append(p.reshape(3, L))
         lens.append(L)
         deltas.append(int(np.asarray(f.rope_deltas).reshape(-1)[0]) if f.rope_deltas is not None else 0)
+        ds = deepstack_window(getattr(f, "visual_pos_masks", None), getattr(f, "deepstack_visual_embeds", None), 0, L)
+        if ds is not None:                 # Qwen3-VL: the request's DeepStack rows, numbered in the concatenated prefill
+            ds_embeds.append(ds[0])
+            ds_rows.append(ds[1] + row0)
+        row0 += L
+    if ds_embeds:
+        if deepstack_out is None:
+            raise NotImplementedError("this caller of embed_requests does not carry DeepStack features into its prefill")
+        deepstack_out.append((torch.cat(ds_embeds, dim=1), np.concatenate(ds_rows)))
     return torch.cat(embs, dim=0), np.concatenate(poss, axis=1), lens, deltas
 
 
-def embed_requests(model, input_ids_list, pixel_values_list, grids, extras=None):
+def embed_requests(model, input_ids_list, pixel_values_list, grids, extras=None, deepstack_out=None):
     """Input embeddings of several requests for ONE varlen prefill: one ViT call over the concatenated patches of all
     images (as the reference does per shape group, ar.py:3165-3167), features scattered into each request's
     placeholder rows, per-request M-RoPE positions.  -> (embeds [sum L, D], position_ids [3, sum L], lengths, rope deltas)
-    `extras`: per-request keyword arguments of `get_input_embeddings` besides the pixels (phi3_v: image_sizes)."""
+    `extras`: per-request keyword arguments of `get_input_embeddings` besides the pixels (phi3_v: image_sizes).
+    `deepstack_out`: a list; a family with DeepStack (Qwen3-VL) appends ONE (embeds [n_layers, n_rows, D], rows int64 [n_rows] of
+    the concatenated prefill) for the caller to hand to `lm.prefill(deepstack=...)` - the rows of all requests concatenated."""
+    if getattr(model.language_model, "DEEPSTACK", False):
+        # Qwen3-VL: every request through the model's own get_input_embeddings (its tower call returns the taps beside the features)
+        extras = [dict(e or {}, **({"image_grid_thw": g} if g is not None else {}))
+                  for e, g in zip(extras or [None] * len(grids), grids)]
+        return _embed_requests_per_model(model, input_ids_list, pixel_values_list, extras, deepstack_out)
     if not hasattr(model, "merge_input_ids_with_image_features"):
         return _embed_requests_per_model(model, input_ids_list, pixel_values_list, extras or [None] * len(input_ids_list))
     lm = model.language_model
@@ -850,11 +876,13 @@ def batch_generate_ids(model, input_ids_list: List[np.ndarray], pixel_values_lis
         idxs = order[i:i + B]
         i += B
         t0 = time.perf_counter()
+        ds = []
         emb_cat, pos_cat, lens, deltas = embed_requests(model, [input_ids_list[j] for j in idxs],
                                                         [pixel_values_list[j] for j in idxs], [grids[j] for j in idxs],
-                                                        extras=[extras[j] for j in idxs] if extras else None)
+                                                        extras=[extras[j] for j in idxs] if extras else None, deepstack_out=ds)
         caches = lm.make_cache_batch(len(idxs))
-        logits = lm.prefill(emb_cat, pos_cat, caches, lens, "last", reserve_extra=max_tokens + 2)
+        logits = lm.prefill(emb_cat, pos_cat, caches, lens, "last", reserve_extra=max_tokens + 2,
+                            **({"deepstack": ds[0]} if ds else {}))
         step0 = torch.zeros(1, dtype=torch.int32, device=logits.device)
         tok0, _ = ops.sample(logits, step=step0, want_logprobs=False, **sargs)
         st = lm.decode_begin(caches, tok0, deltas, max_new_tokens=max_tokens + 1)

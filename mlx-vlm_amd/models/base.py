@@ -48,3 +48,32 @@ class BaseModelConfig:
 
     def to_dict(self):
         return {k: v for k, v in self.__dict__.items() if v is not None}
+
+
+def deepstack_window(visual_pos_masks, deepstack_visual_embeds, start: int, window: int):
+    """DeepStack inputs of ONE prefill call over prompt columns [start, start + window) (reference qwen3_vl/language.py:528-558:
+    the full-prompt mask and embeds are cut to the model's current window; the embeds of a layer are consumed in row order).
+    visual_pos_masks: bool [B, L] (or [L]) over the full prompt; deepstack_visual_embeds: [n_layers, n_visual, D] (tensor or
+    list of per-layer tensors).  -> (embeds [n_layers, n_window, D], rows int64 [n_window] into the call's B * window rows), or
+    None when there is nothing to add.  A window that cuts the prompt is taken for one sequence, as the reference does."""
+    import numpy as np
+
+    if deepstack_visual_embeds is None or visual_pos_masks is None or len(deepstack_visual_embeds) == 0:
+        return None
+    m = visual_pos_masks.detach().cpu().numpy() if hasattr(visual_pos_masks, "detach") else np.asarray(visual_pos_masks)
+    m = m.astype(bool).reshape(1, -1) if m.ndim == 1 else m.astype(bool)
+    start, window = int(start), int(window)
+    whole = start == 0 and window >= m.shape[1]
+    if not whole and m.shape[0] != 1:
+        raise NotImplementedError("DeepStack over a window of a batched prompt: one sequence per chunked prefill")
+    n_before = int(m[:, :start].sum())
+    win = m[:, start:start + window]
+    rows = np.nonzero(win.reshape(-1))[0].astype(np.int64)
+    if rows.size == 0:
+        return None
+    e = deepstack_visual_embeds
+    if isinstance(e, (list, tuple)):
+        import torch
+
+        e = torch.stack(list(e))
+    return e[:, n_before:n_before + rows.size], rows

@@ -27,7 +27,7 @@ import torch
 
 from ... import _lib, ops
 from ..._lib import check
-from ..base import LanguageModelOutput
+from ..base import LanguageModelOutput, deepstack_window
 from ..cache import PAGE, Arena, KVCache, KVPool, PagedSequence
 from .config import ModelConfig, TextConfig
 
@@ -296,6 +296,7 @@ class LanguageModel:
         check(L.vlm_llm_create(C.byref(cfg), C.byref(h)), "llm_create")
         self._handle = h
         self.apply_tuning()
+        self._set_engine_modes()           # (before the first vlm_llm_set_layer: a mode decides what the engine reads of a layer)
         for i in range(t.num_hidden_layers):
             p = f"model.layers.{i}."
             qkv_parts = [lin(p + "self_attn.q_proj"), lin(p + "self_attn.k_proj"), lin(p + "self_attn.v_proj")]
@@ -306,7 +307,7 @@ class LanguageModel:
             else:
                 wqkv = big(torch.cat(qkv_parts, dim=0))
             bqkv = torch.cat([g(p + "self_attn.q_proj.bias"), g(p + "self_attn.k_proj.bias"),
-                              g(p + "self_attn.v_proj.bias")], dim=0).contiguous()
+                              g(p + "self_attn.v_proj.bias")], dim=0).contiguous() if self.QKV_BIAS else None
             gate, up = lin(p + "mlp.gate_proj"), lin(p + "mlp.up_proj")
             wo = big(lin(p + "self_attn.o_proj"))
             if isinstance(gate, Qz.QuantW) != isinstance(up, Qz.QuantW):
@@ -314,7 +315,7 @@ class LanguageModel:
             wgu = Qz.interleave_rows(gate, up) if isinstance(gate, Qz.QuantW) else \
                 big(torch.stack([gate, up], dim=1).reshape(2 * t.intermediate_size, t.hidden_size))
             del gate, up
-            bqkv = self.arena.put(bqkv)
+            bqkv = self.arena.put(bqkv) if bqkv is not None else None
             ws = dict(ln1=self.arena.put(g(p + "input_layernorm.weight")), wqkv=wqkv, bqkv=bqkv, wo=wo,
                       ln2=self.arena.put(g(p + "post_attention_layernorm.weight")), wgu=wgu,
                       wdown=big(lin(p + "mlp.down_proj")))
@@ -327,8 +328,9 @@ class LanguageModel:
             def sp(x):
                 return x.sb.data_ptr() if isinstance(x, Qz.QuantW) else None
 
-            lay = _lib.LlmLayer(ws["ln1"].data_ptr(), wp(wqkv), bqkv.data_ptr(), wp(ws["wo"]), ws["ln2"].data_ptr(), wp(wgu),
-                                wp(ws["wdown"]), sp(wqkv), sp(ws["wo"]), sp(wgu), sp(ws["wdown"]))
+            lay = _lib.LlmLayer(ws["ln1"].data_ptr(), wp(wqkv), bqkv.data_ptr() if bqkv is not None else None, wp(ws["wo"]),
+                                ws["ln2"].data_ptr(), wp(wgu), wp(ws["wdown"]), sp(wqkv), sp(ws["wo"]), sp(wgu), sp(ws["wdown"]),
+                                *self._layer_extra(i, p, W))
             check(L.vlm_llm_set_layer(h, i, C.byref(lay)), "llm_set_layer")
         def pad_rows8(x):
             """the head (and a tied embedding) gets zero rows up to a multiple of 8: the prefill logits GEMM runs over them"""
@@ -383,6 +385,15 @@ class LanguageModel:
     # nobody reads) were not positive in both series alone: off, behind their switches
     TUNING_DEFAULTS = {"fused_tail": 1, "mfma_gemv": 1, "attn_pagesplit": 16, "gemv_variant": 6669 | 64 | 8192, "attn_merge": 1,
                        "host_ring": 1, "skip_logprobs": 0}
+
+    QKV_BIAS = True             # q / k / v projections carry a bias (Qwen2); a family without one (Qwen3) hands the engine NULL
+
+    def _set_engine_modes(self):
+        """vlm_llm_set_tuning mode keys of the family, set between vlm_llm_create and the first vlm_llm_set_layer"""
+
+    def _layer_extra(self, i, prefix, W):
+        """the fields a family appends to vlm_llm_layer (read by the engine in that family's mode only)"""
+        return ()
 
     def apply_tuning(self, **over):
         L = _lib.lib()
@@ -513,11 +524,14 @@ class LanguageModel:
 
     # ------------------------------------------------------------------ prefill over concatenated sequences
     def prefill(self, inputs_embeds: torch.Tensor, position_ids: np.ndarray, caches: List[List[KVCache]],
-                lengths: List[int], logits_rows: str = "last", reserve_extra: int = 0, paged_attn: bool = False) -> torch.Tensor:
+                lengths: List[int], logits_rows: str = "last", reserve_extra: int = 0, paged_attn: bool = False,
+                deepstack=None) -> torch.Tensor:
         """inputs_embeds [T, D] (sequences concatenated, lengths[i] tokens each); position_ids int [3, T];
         caches[i] = the layer views of sequence i (appended after their current offset).
         paged_attn: chunks onto NON-EMPTY bf16 caches attend straight over the pages (ops.attn_prefill_paged) instead of over a
         gathered copy - the warm admission of the batch generator's prefix cache; every other caller leaves it False.
+        deepstack (a family with DEEPSTACK only): (embeds bf16 [n_layers_ds, n_rows, D], rows int [n_rows]) - after decoder layer
+        i < n_layers_ds the rows `rows` of the T rows of THIS call get embeds[i] added (reference qwen3_vl/language.py:231-283).
         -> logits [n_seq, V] (logits_rows == "last") or [T, V] ("all")."""
         t, dev = self.args, self.device
         T, D = inputs_embeds.shape
@@ -525,7 +539,8 @@ class LanguageModel:
         seqs = [c[0]._seq for c in caches]
         if any(s.offset != 0 for s in seqs):
             return self._prefill_onto_cache(inputs_embeds, position_ids, caches, lengths, logits_rows, reserve_extra,
-                                            paged_attn=paged_attn)
+                                            paged_attn=paged_attn, deepstack=deepstack)
+        ds = self._deepstack_device(deepstack, T)
         cu = np.concatenate([[0], np.cumsum(lengths)]).astype(np.int32)
         kv_seq = np.concatenate([np.full(n, s.seq, dtype=np.int32) for n, s in zip(lengths, seqs)])
         kv_slot = np.concatenate([np.arange(n, dtype=np.int32) for n in lengths])
@@ -563,14 +578,41 @@ class LanguageModel:
         a = _lib.PrefillArgs(h.data_ptr(), T, pos_d[0].data_ptr(), pos_d[1].data_ptr(), pos_d[2].data_ptr(),
                              kv_seq_d.data_ptr(), kv_slot_d.data_ptr(), cu_d.data_ptr(), len(lengths), nqb,
                              xn.data_ptr(), qkv.data_ptr(), attn.data_ptr(), act.data_ptr(), rows_d.data_ptr(),
-                             len(rows), xlast.data_ptr(), logits.data_ptr(), int(bool(getattr(self, "_prefill_rope_long", False))))
+                             len(rows), xlast.data_ptr(), logits.data_ptr(), int(bool(getattr(self, "_prefill_rope_long", False))),
+                             *((ds[0].data_ptr(), ds[1].data_ptr(), ds[0].shape[0], ds[0].shape[1]) if ds is not None else ()))
         check(_lib.lib().vlm_llm_prefill(self._handle, C.byref(a), C.c_void_p(torch.cuda.current_stream().cuda_stream)),
               "llm_prefill")
         for n, s in zip(lengths, seqs):
             s.offset += n
             s.note_prefill(n)
-        self._keep = (h, xn, qkv, attn, act, xlast, pos_d, meta, rows_d)  # keep alive until the stream has run
+        self._keep = (h, xn, qkv, attn, act, xlast, pos_d, meta, rows_d, ds)  # keep alive until the stream has run
         return logits
+
+    DEEPSTACK = False           # does the engine mode of this family read vlm_prefill_args' DeepStack fields (Qwen3-VL)?
+
+    def _deepstack_device(self, deepstack, T):
+        """(embeds, rows) of a prefill call -> (contiguous bf16 [n, R, D] device tensor, int32 [R] device rows), or None"""
+        if deepstack is None:
+            return None
+        if not self.DEEPSTACK:
+            raise NotImplementedError(f"{type(self).__module__}: DeepStack embeddings are a Qwen3-VL input")
+        embeds, rows = deepstack
+        rows = np.asarray(_to_np(rows), dtype=np.int64).reshape(-1)
+        if embeds is None or rows.size == 0 or len(embeds) == 0:
+            return None
+        embeds = embeds if isinstance(embeds, torch.Tensor) else torch.stack(list(embeds))
+        if embeds.dim() != 3 or embeds.shape[1] != rows.size or embeds.shape[2] != self.args.hidden_size:
+            raise ValueError(f"deepstack embeds {tuple(embeds.shape)} do not match {rows.size} rows of width {self.args.hidden_size}")
+        if embeds.shape[0] > self.args.num_hidden_layers or rows.min() < 0 or rows.max() >= T or np.unique(rows).size != rows.size:
+            raise ValueError("deepstack rows must be distinct rows of the call, the embeds at most one set per decoder layer")
+        return (embeds.to(device=self.device, dtype=torch.bfloat16).contiguous(), _lib.h2d(rows.astype(np.int32), self.device))
+
+    def _rope_kvwrite(self, i, qkv, pos_d, inv_tab, new_seq_d, new_slot_d, bt, kp, vp):
+        """rotary embedding of layer i's q / k rows in place + their K / V into the pages (the prompt-chunk layer loop)"""
+        t, sec = self.args, self.mrope_section
+        ops.mrope_kvwrite_(qkv, t.num_attention_heads, t.num_key_value_heads, self.head_dim, pos_d[0], pos_d[1], pos_d[2], inv_tab,
+                           int(sec[0]), int(sec[1]), kv_seq=new_seq_d, kv_slot=new_slot_d, block_table=bt, kpool=kp, vpool=vp,
+                           qk_scale=getattr(t, "rope_qk_scale", None))
 
     def _layer_weights(self, i):
         """layer i's weights by the names of self._w; of a 4-bit model only THIS layer's matrices are dequantised"""
@@ -578,7 +620,8 @@ class LanguageModel:
             return self._w
         return {k: dense(v) for k, v in self._w.items() if k.startswith(f"{i}.")}
 
-    def _prefill_onto_cache(self, inputs_embeds, position_ids, caches, lengths, logits_rows, reserve_extra, paged_attn=False):
+    def _prefill_onto_cache(self, inputs_embeds, position_ids, caches, lengths, logits_rows, reserve_extra, paged_attn=False,
+                            deepstack=None):
         """A prompt chunk appended to a NON-EMPTY cache: chunked prefill (reference ar.py:426-472), `prompt_cache=` continuation
         across calls, i.e. multi-turn (dispatch.py:861-882, common.py:243-263), a chunk onto a QuantizedKVCache (an update of any
         length, then quantized_scaled_dot_product_attention: cache.py:233-334, base.py:260-302) and the warm admission of the
@@ -696,20 +739,21 @@ class LanguageModel:
                 return attn[new_rows_d].contiguous()
 
         h = inputs_embeds.contiguous().clone()
-        sec = self.mrope_section
+        ds = self._deepstack_device(deepstack, T)
         inv_tab = self._w["inv_freq"][hd // 2:] if getattr(self, "_prefill_rope_long", False) else self._w["inv_freq"]   # SuScaledRoPE regime of this call
-        qk_scale = getattr(t, "rope_qk_scale", None)
         for i in range(t.num_hidden_layers):
             w = self._layer_weights(i)
             kp, vp = pool.kpool[i], pool.vpool[i]          # this layer's K / V pools (flat views)
             xn = ops.rmsnorm(h, w[f"{i}.ln1"], t.rms_norm_eps)
-            qkv = ops.gemm(xn, w[f"{i}.wqkv"], bias=w[f"{i}.bqkv"], epilogue=ops.EPI_BIAS)
-            ops.mrope_kvwrite_(qkv, Hq, Hkv, hd, pos_d[0], pos_d[1], pos_d[2], inv_tab, int(sec[0]), int(sec[1]), kv_seq=new_seq_d,
-                               kv_slot=new_slot_d, block_table=bt, kpool=kp, vpool=vp, qk_scale=qk_scale)
+            bqkv = w[f"{i}.bqkv"]
+            qkv = ops.gemm(xn, w[f"{i}.wqkv"], bias=bqkv, epilogue=ops.EPI_BIAS if bqkv is not None else ops.EPI_NONE)
+            self._rope_kvwrite(i, qkv, pos_d, inv_tab, new_seq_d, new_slot_d, bt, kp, vp)
             h = ops.gemm(attend(i, qkv, kp, vp), w[f"{i}.wo"], res=h, epilogue=ops.EPI_RESIDUAL)
             xn = ops.rmsnorm(h, w[f"{i}.ln2"], t.rms_norm_eps)
             act = ops.gemm(xn, w[f"{i}.wgu"], epilogue=ops.EPI_SWIGLU)
             h = ops.gemm(act, w[f"{i}.wdown"], res=h, epilogue=ops.EPI_RESIDUAL)
+            if ds is not None and i < ds[0].shape[0]:
+                ops.add_rows_(ds[0][i], ds[1], h)          # DeepStack: the chunk's image rows (reference language.py:231-283)
         rows = (cu_new[1:] - 1) if logits_rows == "last" else np.arange(T)
         xl = ops.rmsnorm(h[_lib.h2d(rows.astype(np.int64), dev)].contiguous(), self._w["norm"], t.rms_norm_eps)
         logits = ops.gemm(xl, dense(self._w["head"]))[:, : t.vocab_size]      # (the head is dequantised once, here)
@@ -1057,6 +1101,9 @@ class LanguageModel:
         video_grid_thw = kwargs.pop("video_grid_thw", None)
         rope_deltas_kw = kwargs.pop("rope_deltas", None)
         logits_to_keep = kwargs.pop("logits_to_keep", None)
+        # DeepStack (Qwen3-VL; every other family's InputEmbeddingsFeatures carries None): full-prompt mask + per-layer embeds
+        visual_pos_masks = kwargs.pop("visual_pos_masks", None)
+        deepstack_visual_embeds = kwargs.pop("deepstack_visual_embeds", None)
         if pixel_values is not None:
             self._rope_deltas = None
             self._position_ids = None
@@ -1128,7 +1175,12 @@ class LanguageModel:
             inputs_embeds = self.embed_tokens(ids)
         emb = inputs_embeds.reshape(B * Lq, -1)
         pos_flat = pos.reshape(3, B * Lq)
-        logits = self.prefill(emb, pos_flat, caches, [Lq] * B, logits_rows="last" if logits_to_keep == 1 else "all")
+        more = {}
+        if deepstack_visual_embeds is not None:
+            ds = deepstack_window(visual_pos_masks, deepstack_visual_embeds, cache_offset, Lq)
+            if ds is not None:
+                more["deepstack"] = ds
+        logits = self.prefill(emb, pos_flat, caches, [Lq] * B, logits_rows="last" if logits_to_keep == 1 else "all", **more)
         if logits_to_keep == 1:
             return LanguageModelOutput(logits=logits.view(B, 1, -1))
         return LanguageModelOutput(logits=logits.view(B, Lq, -1))

@@ -15,6 +15,7 @@ from . import _lib
 from ._lib import check
 
 EPI_NONE, EPI_BIAS, EPI_GELU_FAST, EPI_GELU_ERF, EPI_RESIDUAL, EPI_SWIGLU = 0, 1, 2, 4, 8, 16
+EPI_GELU_TANH = 256                     # nn.GELU(approx="tanh") (the Qwen3-VL tower's MLP); gemm only
 
 
 def _p(t: Optional[torch.Tensor]):
@@ -199,6 +200,29 @@ def mrope_kvwrite_(qkv, Hq, Hkv, D, pos_t, pos_h, pos_w, inv_freq, sec0, sec1, k
     check(_lib.lib().vlm_mrope_kvwrite(_p(qkv), qkv.stride(0), T, Hq, Hkv, D, _p(pos_t), _p(pos_h), _p(pos_w),
                                        _p(inv_freq), sec0, sec1, _p(kv_seq), _p(kv_slot), _p(block_table), max_pages,
                                        _p(kpool), _p(vpool), _stream()), "mrope_kvwrite")
+    return qkv
+
+
+def qknorm_table(inv_freq, eps, q_norm_w, k_norm_w):
+    """the fp32 table mrope_qknorm_kvwrite_ reads: [D / 2 inv_freq | eps | D q_norm_w | D k_norm_w] (include/vlm_hip.h)"""
+    f = torch.float32
+    return torch.cat([inv_freq.to(f).reshape(-1), torch.tensor([float(eps)], dtype=f, device=inv_freq.device),
+                      q_norm_w.to(f).reshape(-1), k_norm_w.to(f).reshape(-1)]).contiguous()
+
+
+def mrope_qknorm_kvwrite_(qkv, Hq, Hkv, D, pos_t, pos_h, pos_w, table, mrope_section, kv_seq=None, kv_slot=None, block_table=None,
+                          kpool=None, vpool=None):
+    """The QK-norm form of mrope_kvwrite_ (Qwen3-VL): per q / k head RMSNorm(head_dim), the interleaved M-RoPE selector over
+    mrope_section, rotation, q in place, k / v into the pools.  vlm_mrope_kvwrite_scaled with a negative mrope_sec0; `table`
+    from qknorm_table.  D == 128."""
+    _dev(qkv, pos_t, pos_h, pos_w, table, kv_seq, kv_slot, block_table, kpool, vpool)
+    s0, s1, s2 = (int(v) for v in mrope_section)
+    if s0 <= 0 or s0 + s1 + s2 != D // 2 or table.dtype != torch.float32 or table.numel() != D // 2 + 1 + 2 * D:
+        raise ValueError("mrope_qknorm_kvwrite_: mrope_section sums to D / 2 (first entry > 0), table = qknorm_table(...)")
+    check(_lib.lib().vlm_mrope_kvwrite_scaled(_p(qkv), qkv.stride(0), qkv.shape[0], Hq, Hkv, D, _p(pos_t), _p(pos_h), _p(pos_w),
+                                              _p(table), -s0, s1, _p(kv_seq), _p(kv_slot), _p(block_table),
+                                              block_table.shape[1] if block_table is not None else 0, _p(kpool), _p(vpool), 1.0,
+                                              _stream()), "mrope_qknorm_kvwrite")
     return qkv
 
 
@@ -453,6 +477,18 @@ def scatter_rows_(src, dst_rows, dst):
     _dev(src, dst_rows, dst)
     check(_lib.lib().vlm_scatter_image_rows(_p(src), _p(dst_rows), _p(dst), src.shape[0], src.shape[1], src.stride(0),
                                             dst.stride(0), _stream()), "scatter_rows")
+    return dst
+
+
+def add_rows_(src, dst_rows, dst):
+    """dst[dst_rows[i]] += src[i], one typed bf16 add per element (DeepStack); dst_rows int32, distinct.  The add form of
+    vlm_scatter_image_rows (a negative row count)."""
+    _dev(src, dst_rows, dst)
+    if dst_rows.dtype != torch.int32 or dst_rows.numel() != src.shape[0] or src.shape[1] != dst.shape[1]:
+        raise ValueError("add_rows_: src [n, D], dst_rows int32 [n], dst [*, D]")
+    if src.shape[0]:
+        check(_lib.lib().vlm_scatter_image_rows(_p(src), _p(dst_rows), _p(dst), -src.shape[0], src.shape[1], src.stride(0),
+                                                dst.stride(0), _stream()), "add_rows")
     return dst
 
 

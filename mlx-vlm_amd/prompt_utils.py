@@ -3,7 +3,7 @@
 `apply_chat_template` 829-995) for the message formats those families use:
 
     qwen2_vl, idefics2            content = [text item, image items ...]            (LIST_WITH_IMAGE)
-    qwen2_5_vl                    content = [image items ..., text item]            (LIST_WITH_IMAGE_FIRST)
+    qwen2_5_vl, qwen3_vl          content = [image items ..., text item]            (LIST_WITH_IMAGE_FIRST)
     llava-qwen2 / bunny-llama     content = "<image>\\n" * n + prompt, one image     (IMAGE_TOKEN_NEWLINE, single-image models)
     phi3_v                        content = "<|image_1|><|image_2|>..." + prompt    (NUMBERED_IMAGE_TOKENS)
     anything else                 plain text messages
@@ -19,6 +19,7 @@ from typing import Any, Dict, List, Union
 # model_type -> (kind, token).  kind: "list" = typed content list ("list_first": image items in front of the text item),
 # "token" = marker text in front of the prompt, "numbered" = <|image_N|> markers
 _FORMATS = {"qwen2_vl": ("list", None), "idefics2": ("list", None), "qwen2_5_vl": ("list_first", None),
+            "qwen3_vl": ("list_first", None),
             "llava-qwen2": ("token", "<image>\n"), "bunny-llama": ("token", "<image>\n"),
             "phi3_v": ("numbered", None)}
 _SINGLE_IMAGE_ONLY = {"llava-qwen2", "bunny-llama"}

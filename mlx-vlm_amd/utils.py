@@ -22,7 +22,8 @@ import torch
 # model_type aliases of the reference (utils.py:34-62): the checkpoint's `model_type` -> package under models/.  The
 # whole alias table is kept so that a lookup resolves exactly as it does there; families that are not built here then
 # fail in get_model_and_args with the reference's own "Model type ... not supported." (utils.py:633-635).
-# Built: qwen2_vl, qwen2_5_vl, phi3_v, idefics2, llava_bunny (nanoLLaVA ships `model_type: "llava-qwen2"`, Bunny `"bunny-llama"`).
+# Built: qwen2_vl, qwen2_5_vl, qwen3_vl (dense; qwen3_vl_moe is refused), phi3_v, idefics2, llava_bunny (nanoLLaVA ships
+# `model_type: "llava-qwen2"`, Bunny `"bunny-llama"`).
 MODEL_REMAPPING: Dict[str, str] = {
     "llava-qwen2": "llava_bunny", "bunny-llama": "llava_bunny", "llava_qwen2": "fastvlm", "lfm2-vl": "lfm2_vl",
     "cohere2_vision": "aya_vision", "jvlm": "jina_vlm", "phi4-siglip": "phi4_siglip", "sam3_video": "sam3",
@@ -39,6 +40,8 @@ def get_model_and_args(config: dict):
     """reference utils.py:588-635"""
     model_type = config["model_type"].lower()
     model_type = MODEL_REMAPPING.get(model_type, model_type)
+    if model_type == "qwen3_vl_moe":
+        raise NotImplementedError("qwen3_vl_moe: the dense Qwen3-VL family is built, its mixture-of-experts variant is not")
     try:
         arch = importlib.import_module(f"{__package__}.models.{model_type}")
     except ImportError as e:
@@ -245,7 +248,13 @@ def load_processor(model_path: str, config, image_preprocess: str = "host"):
                 ip_kwargs[k] = pc[k]
     if image_preprocess == "device":
         ip_kwargs["device"] = "cuda"
-    if MODEL_REMAPPING.get(mt, mt) == "qwen2_5_vl":
+    if MODEL_REMAPPING.get(mt, mt) == "qwen3_vl":
+        # reference qwen3_vl/processing_qwen3_vl.py: the same numpy image processor with patch 16 (merge 2, mean / std of
+        # preprocessor_config.json, 0.5 by default) + the Qwen2-VL placeholder expansion
+        from .models.qwen3_vl.processing_qwen3_vl import Qwen3VLImageProcessor, Qwen3VLProcessor
+
+        proc = Qwen3VLProcessor(Qwen3VLImageProcessor(**ip_kwargs), tok)
+    elif MODEL_REMAPPING.get(mt, mt) == "qwen2_5_vl":
         # reference qwen2_5_vl/processing_qwen2_5_vl.py: the Qwen2-VL image processor (patch 14) + mm_token_type_ids on request
         from .models.qwen2_5_vl.processing_qwen2_5_vl import Qwen2_5_VLProcessor
 
