@@ -766,135 +766,107 @@ extern "C" int vlm_vit_set_globals(void* handle, const vlm_vit_globals* g) {
   return 0;
 }
 
-// The Qwen3-VL form of the tower (VLM_VIT_FORM_QWEN3; reference qwen3_vl/vision.py:106-123,164-191,379-425): the first form's
-// LayerNorm block with a tanh-GELU MLP, a biased patch projection with the interpolated position rows added behind it, and a
-// post-shuffle PatchMerger (LayerNorm over the 2 x 2 merge unit's 4E values) behind every DeepStack tap block.
-static int vit_forward_qwen3(const Vit* v, const vlm_vit_args* a, void* stream) {
-  const vlm_vit_config& c = v->cfg;
-  const int E = c.embed_dim, H = c.n_heads, hd = E / H, N = a->N, MH = c.mlp_hidden;
-  const int mm = c.merge * c.merge;
-  if (N % mm != 0 || (hd != 64 && hd != 80 && hd != 128) || (long)E * mm > 8192) return 2;      // (rope2d epilogue, attention, LayerNorm)
-  if (!(c.qk_interleaved & VLM_VIT_QK_INTERLEAVED) ||
-      a->sin_tab != off(const_cast<void*>(a->cos_tab), (size_t)N * (hd / 2) * sizeof(float)))
-    return 1;                             // this form has the rope in the qkv GEMM epilogue only
-  if (!a->cu_seqlens || !a->pos_rows || !v->g.bpatch) return 1;
-  int n_taps = 0;
-  for (const vlm_vit_block& w : v->blocks) n_taps += w.tap_w0 != nullptr;
-  if (n_taps != a->n_taps || (n_taps > 0 && !a->tap_out)) return 1;
-  const float scale = 1.0f / sqrtf((float)hd);
-  const int Nm = N / mm, EM = E * mm;
-  // x = T(T(patches Wp^T + b) + pos_rows): the reference's two typed ops (vision.py:386-388) are the epilogue's two roundings
-  TRY(vlm_gemm_bf16(a->patches, v->g.wpatch, v->g.bpatch, a->pos_rows, a->x, N, E, c.patch_k, c.patch_k, c.patch_k, E, E,
-                    VLM_EPI_BIAS | VLM_EPI_RESIDUAL, stream));
-  int tap = 0;
-  for (int i = 0; i < c.depth; ++i) {
-    const vlm_vit_block& w = v->blocks[i];
-    TRY(vlm_layernorm(a->x, w.ln1_w, w.ln1_b, a->xn, N, E, c.ln_eps, stream));
-    TRY(vlm_gemm_bf16_rope2d(a->xn, w.wqkv, w.bqkv, a->cos_tab, a->qkv, N, 3 * E, E, E, E, 3 * E, hd, 2 * E, stream));
-    TRY(vlm_attn_prefill(a->qkv, off(a->qkv, (size_t)E * 2), off(a->qkv, (size_t)2 * E * 2), a->attn, 3 * E, 3 * E, 3 * E, E,
-                         a->cu_seqlens, a->nseg, a->total_qblocks, H, H, hd, scale, a->uniform_segments ? 2 : 0, stream));
-    TRY(vlm_gemm_bf16(a->attn, w.wproj, w.bproj, a->x, a->x, N, E, E, E, E, E, E, VLM_EPI_BIAS | VLM_EPI_RESIDUAL, stream));
-    TRY(vlm_layernorm(a->x, w.ln2_w, w.ln2_b, a->xn, N, E, c.ln_eps, stream));
-    TRY(vlm_gemm_bf16(a->xn, w.wfc1, w.bfc1, nullptr, a->mlp, N, MH, E, E, E, MH, 0, VLM_EPI_BIAS | VLM_EPI_GELU_TANH, stream));
-    TRY(vlm_gemm_bf16(a->mlp, w.wfc2, w.bfc2, a->x, a->x, N, E, MH, MH, MH, E, E, VLM_EPI_BIAS | VLM_EPI_RESIDUAL, stream));
-    if (w.tap_w0) {
-      // DeepStack tap: LayerNorm over [N/4][4E] (post-shuffle), Linear + GELU(erf), Linear -> tap_out[tap]
-      TRY(vlm_layernorm(a->x, w.tap_ln_w, w.tap_ln_b, a->xn, Nm, EM, c.ln_eps, stream));
-      TRY(vlm_gemm_bf16(a->xn, w.tap_w0, w.tap_b0, nullptr, a->mrg, Nm, EM, EM, EM, EM, EM, 0, VLM_EPI_BIAS | VLM_EPI_GELU_ERF, stream));
-      TRY(vlm_gemm_bf16(a->mrg, w.tap_w2, w.tap_b2, nullptr, off(a->tap_out, (size_t)tap * Nm * c.out_dim * 2), Nm, c.out_dim, EM, EM,
-                        EM, c.out_dim, 0, VLM_EPI_BIAS, stream));
-      ++tap;
-    }
-  }
-  TRY(vlm_layernorm(a->x, v->g.ln_q_w, v->g.ln_q_b, a->xn, N, E, c.ln_eps, stream));
-  TRY(vlm_gemm_bf16(a->xn, v->g.wm0, v->g.bm0, nullptr, a->mrg, Nm, EM, EM, EM, EM, EM, 0, VLM_EPI_BIAS | VLM_EPI_GELU_ERF, stream));
-  TRY(vlm_gemm_bf16(a->mrg, v->g.wm2, v->g.bm2, nullptr, a->out, Nm, c.out_dim, EM, EM, EM, c.out_dim, 0, VLM_EPI_BIAS, stream));
-  return 0;
+// The three Qwen towers are ONE loop (reference qwen2_vl/vision.py:257-290, qwen2_5_vl/vision.py:177-193,326-393,
+// qwen3_vl/vision.py:106-123,164-191,379-425): patch GEMM -> depth x [norm, qkv GEMM + bias + 2-D rope, attention, proj GEMM +
+// bias + residual, norm, fc1 GEMM + bias + activation, fc2 GEMM + bias + residual] -> PatchMerger.  What a form changes:
+namespace {
+struct VitForm {
+  bool rms;        // RMSNorm (weight only) in the blocks and the merger, not LayerNorm
+  int fc1_epi;     // the MLP's activation epilogue
+  int fc1_rows;    // fc1 rows per MLP unit: 2 = the (gate, up) pairs VLM_EPI_SWIGLU folds into one column
+  bool patch_pos;  // the patch GEMM adds bpatch and pos_rows: x = T(T(patches Wp^T + b) + pos_rows), the reference's two typed ops
+  bool windowed;   // rows in WINDOW order between two device gathers; blocks outside fullatt_mask attend over the window table
+  bool taps;       // a post-shuffle PatchMerger (norm over the merge unit's merge^2 E values) behind every block with tap_w0
+};
+
+VitForm vit_form(int flags) {
+  if (flags & VLM_VIT_FORM_QWEN2_5) return {true, VLM_EPI_SWIGLU, 2, false, true, false};
+  if (flags & VLM_VIT_FORM_QWEN3) return {false, VLM_EPI_GELU_TANH, 1, true, false, true};
+  return {false, VLM_EPI_GELU_FAST, 1, false, false, false};
 }
 
-// The Qwen2.5-VL form of the tower (VLM_VIT_FORM_QWEN2_5; reference qwen2_5_vl/vision.py:177-193,326-393): RMSNorm blocks with a
-// biased SwiGLU MLP, window attention in all but the fullatt blocks, the rows in window order between two device gathers.
-static int vit_forward_qwen2_5(const Vit* v, const vlm_vit_args* a, void* stream) {
-  const vlm_vit_config& c = v->cfg;
-  const int E = c.embed_dim, H = c.n_heads, hd = E / H, N = a->N, MH = c.mlp_hidden;
-  const int mm = c.merge * c.merge;
-  if (N % mm != 0 || hd % 16 != 0 || c.depth > 64 || (long)c.out_dim > (long)mm * MH) return 2;
-  if (!(c.qk_interleaved & VLM_VIT_QK_INTERLEAVED) ||
-      a->sin_tab != off(const_cast<void*>(a->cos_tab), (size_t)N * (hd / 2) * sizeof(float)))
-    return 1;                             // this form has the rope in the qkv GEMM epilogue only
-  if (!a->win_cu_seqlens || !a->window_index || !a->reverse_index || !a->cu_seqlens || a->win_nseg <= 0) return 1;
-  const bool one_tile = a->win_one_tile != 0;
-  if (one_tile && (a->win_max_seg > 64 || hd != 80)) return 2;
-  const float scale = 1.0f / sqrtf((float)hd);
-  const int Nm = N / mm, EM = E * mm;
-  // patch projection into the attn workspace, then the merge units into window order (hidden_states[window_index], 349-353)
-  TRY(vlm_gemm_bf16(a->patches, v->g.wpatch, nullptr, nullptr, a->attn, N, E, c.patch_k, c.patch_k, c.patch_k, E, 0, VLM_EPI_NONE, stream));
-  TRY(vlm_embed_gather(a->window_index, a->attn, a->x, Nm, EM, EM, Nm, stream));
-  for (int i = 0; i < c.depth; ++i) {
-    const vlm_vit_block& w = v->blocks[i];
-    const bool full = (a->fullatt_mask >> i) & 1ull;
-    TRY(vlm_rmsnorm_residual(a->x, nullptr, w.ln1_w, a->xn, nullptr, N, E, c.ln_eps, stream));
-    TRY(vlm_gemm_bf16_rope2d(a->xn, w.wqkv, w.bqkv, a->cos_tab, a->qkv, N, 3 * E, E, E, E, 3 * E, hd, 2 * E, stream));
-    void* kq = off(a->qkv, (size_t)E * 2);
-    void* vq = off(a->qkv, (size_t)2 * E * 2);
-    if (full)
-      TRY(vlm_attn_prefill(a->qkv, kq, vq, a->attn, 3 * E, 3 * E, 3 * E, E, a->cu_seqlens, a->nseg, a->total_qblocks, H, H, hd, scale,
-                           a->uniform_segments ? 2 : 0, stream));
-    else if (one_tile)
-      TRY(vlm_attn_prefill(a->qkv, kq, vq, a->attn, 3 * E, 3 * E, 3 * E, E, a->win_cu_seqlens, a->win_nseg, a->win_max_seg, H, H, hd,
-                           scale, 8, stream));
-    else
-      TRY(vlm_attn_prefill(a->qkv, kq, vq, a->attn, 3 * E, 3 * E, 3 * E, E, a->win_cu_seqlens, a->win_nseg, a->win_total_qblocks, H, H,
-                           hd, scale, 0, stream));
-    TRY(vlm_gemm_bf16(a->attn, w.wproj, w.bproj, a->x, a->x, N, E, E, E, E, E, E, VLM_EPI_BIAS | VLM_EPI_RESIDUAL, stream));
-    TRY(vlm_rmsnorm_residual(a->x, nullptr, w.ln2_w, a->xn, nullptr, N, E, c.ln_eps, stream));
-    TRY(vlm_gemm_bf16(a->xn, w.wfc1, w.bfc1, nullptr, a->mlp, N, 2 * MH, E, E, E, MH, 0, VLM_EPI_BIAS | VLM_EPI_SWIGLU, stream));
-    TRY(vlm_gemm_bf16(a->mlp, w.wfc2, w.bfc2, a->x, a->x, N, E, MH, MH, MH, E, E, VLM_EPI_BIAS | VLM_EPI_RESIDUAL, stream));
-  }
-  // PatchMerger: RMSNorm -> [N/4, 4E] -> Linear + GELU(erf) -> Linear, then back out of window order (391-392)
-  TRY(vlm_rmsnorm_residual(a->x, nullptr, v->g.ln_q_w, a->xn, nullptr, N, E, c.ln_eps, stream));
-  TRY(vlm_gemm_bf16(a->xn, v->g.wm0, v->g.bm0, nullptr, a->mrg, Nm, EM, EM, EM, EM, EM, 0, VLM_EPI_BIAS | VLM_EPI_GELU_ERF, stream));
-  TRY(vlm_gemm_bf16(a->mrg, v->g.wm2, v->g.bm2, nullptr, a->mlp, Nm, c.out_dim, EM, EM, EM, c.out_dim, 0, VLM_EPI_BIAS, stream));
-  TRY(vlm_embed_gather(a->reverse_index, a->mlp, a->out, Nm, c.out_dim, c.out_dim, Nm, stream));
-  return 0;
+int vit_norm(const VitForm& f, const void* x, const void* w, const void* b, void* y, int rows, int cols, float eps, void* stream) {
+  return f.rms ? vlm_rmsnorm_residual(x, nullptr, w, y, nullptr, rows, cols, eps, stream)
+               : vlm_layernorm(x, w, b, y, rows, cols, eps, stream);
 }
+}  // namespace
 
 extern "C" int vlm_vit_forward(void* handle, const vlm_vit_args* a, void* stream) {
   Vit* v = static_cast<Vit*>(handle);
   if (!v || !a || !a->patches || a->N <= 0) return 1;
-  if ((v->cfg.qk_interleaved & VLM_VIT_FORM_QWEN2_5) && (v->cfg.qk_interleaved & VLM_VIT_FORM_QWEN3)) return 1;
-  if (v->cfg.qk_interleaved & VLM_VIT_FORM_QWEN2_5) return vit_forward_qwen2_5(v, a, stream);
-  if (v->cfg.qk_interleaved & VLM_VIT_FORM_QWEN3) return vit_forward_qwen3(v, a, stream);
   const vlm_vit_config& c = v->cfg;
+  const int newer = c.qk_interleaved & (VLM_VIT_FORM_QWEN2_5 | VLM_VIT_FORM_QWEN3);
+  if (newer == (VLM_VIT_FORM_QWEN2_5 | VLM_VIT_FORM_QWEN3)) return 1;
+  const VitForm f = vit_form(c.qk_interleaved);
   const int E = c.embed_dim, H = c.n_heads, hd = E / H, N = a->N, MH = c.mlp_hidden;
-  const int mm = c.merge * c.merge;
+  const int mm = c.merge * c.merge, Nm = N / mm, EM = E * mm;
+
+  // every refusal before the first launch: shapes (2) ahead of arguments (1), per form in the order it always had
   if (N % mm != 0) return 2;
+  if (f.windowed && (hd % 16 != 0 || c.depth > 64 || (long)c.out_dim > (long)mm * MH)) return 2;   // (out_dim: the merger rows borrow mlp)
+  if (f.taps && ((hd != 64 && hd != 80 && hd != 128) || (long)E * mm > 8192)) return 2;      // (rope2d epilogue, attention, LayerNorm)
+  // the rope runs in the qkv GEMM epilogue over interleaved weights and ONE cos | sin table; only the first form also has a
+  // rope pass of its own, for plain weights
+  const bool interleaved = newer ? (c.qk_interleaved & VLM_VIT_QK_INTERLEAVED) != 0 : c.qk_interleaved != 0;
+  const bool joint = a->sin_tab == off(const_cast<void*>(a->cos_tab), (size_t)N * (hd / 2) * sizeof(float));
+  if (interleaved ? !joint : newer != 0) return 1;
+  if (newer && !a->cu_seqlens) return 1;
+  if (f.windowed) {
+    if (!a->win_cu_seqlens || !a->window_index || !a->reverse_index || a->win_nseg <= 0) return 1;
+    if (a->win_one_tile && (a->win_max_seg > 64 || hd != 80)) return 2;
+  }
+  if (f.patch_pos && (!a->pos_rows || !v->g.bpatch)) return 1;
+  if (f.taps) {
+    int n_taps = 0;
+    for (const vlm_vit_block& w : v->blocks) n_taps += w.tap_w0 != nullptr;
+    if (n_taps != a->n_taps || (n_taps > 0 && !a->tap_out)) return 1;
+  }
+
   const float scale = 1.0f / sqrtf((float)hd);
-  // patch projection (Conv3d with stride == kernel is a GEMM)
-  TRY(vlm_gemm_bf16(a->patches, v->g.wpatch, nullptr, nullptr, a->x, N, E, c.patch_k, c.patch_k, c.patch_k, E, 0, VLM_EPI_NONE, stream));
+  // PatchMerger over `rows` of `cols` (the main one: [N][E], a tap's: [N/4][4E]): norm -> [N/4][4E] -> Linear + GELU(erf) -> Linear
+  auto merger = [&](const void* ln_w, const void* ln_b, int rows, int cols, const void* w0, const void* b0, const void* w2,
+                    const void* b2, void* dst) -> int {
+    TRY(vit_norm(f, a->x, ln_w, ln_b, a->xn, rows, cols, c.ln_eps, stream));
+    TRY(vlm_gemm_bf16(a->xn, w0, b0, nullptr, a->mrg, Nm, EM, EM, EM, EM, EM, 0, VLM_EPI_BIAS | VLM_EPI_GELU_ERF, stream));
+    return vlm_gemm_bf16(a->mrg, w2, b2, nullptr, dst, Nm, c.out_dim, EM, EM, EM, c.out_dim, 0, VLM_EPI_BIAS, stream);
+  };
+
+  // patch projection (Conv3d with stride == kernel is a GEMM); a windowed form projects into the attn workspace and gathers the
+  // merge units into window order (hidden_states[window_index])
+  TRY(vlm_gemm_bf16(a->patches, v->g.wpatch, f.patch_pos ? v->g.bpatch : nullptr, f.patch_pos ? a->pos_rows : nullptr,
+                    f.windowed ? a->attn : a->x, N, E, c.patch_k, c.patch_k, c.patch_k, E, f.patch_pos ? E : 0,
+                    f.patch_pos ? VLM_EPI_BIAS | VLM_EPI_RESIDUAL : VLM_EPI_NONE, stream));
+  if (f.windowed) TRY(vlm_embed_gather(a->window_index, a->attn, a->x, Nm, EM, EM, Nm, stream));
+  int tap = 0;
   for (int i = 0; i < c.depth; ++i) {
     const vlm_vit_block& w = v->blocks[i];
-    TRY(vlm_layernorm(a->x, w.ln1_w, w.ln1_b, a->xn, N, E, c.ln_eps, stream));
-    if (c.qk_interleaved && a->sin_tab == off(const_cast<void*>(a->cos_tab), (size_t)N * (hd / 2) * sizeof(float))) {
-      // 2-D rope in the GEMM epilogue (one HBM pass less per block)
+    TRY(vit_norm(f, a->x, w.ln1_w, w.ln1_b, a->xn, N, E, c.ln_eps, stream));
+    if (interleaved) {                    // 2-D rope in the GEMM epilogue (one HBM pass less per block)
       TRY(vlm_gemm_bf16_rope2d(a->xn, w.wqkv, w.bqkv, a->cos_tab, a->qkv, N, 3 * E, E, E, E, 3 * E, hd, 2 * E, stream));
     } else {
-      if (c.qk_interleaved) return 1;     // interleaved weights need the fused form
       TRY(vlm_gemm_bf16(a->xn, w.wqkv, w.bqkv, nullptr, a->qkv, N, 3 * E, E, E, E, 3 * E, 0, VLM_EPI_BIAS, stream));
       TRY(vlm_rope2d_vision(a->qkv, a->cos_tab, a->sin_tab, N, H, hd, 3 * E, stream));
     }
+    // a window block attends over the window table: one tile per window (flag 8, sized by the longest window) or the general kernel
+    const bool win = f.windowed && !((a->fullatt_mask >> i) & 1ull);
+    const bool one_tile = win && a->win_one_tile != 0;
     TRY(vlm_attn_prefill(a->qkv, off(a->qkv, (size_t)E * 2), off(a->qkv, (size_t)2 * E * 2), a->attn, 3 * E, 3 * E, 3 * E, E,
-                         a->cu_seqlens, a->nseg, a->total_qblocks, H, H, hd, scale, a->uniform_segments ? 2 : 0, stream));
+                         win ? a->win_cu_seqlens : a->cu_seqlens, win ? a->win_nseg : a->nseg,
+                         one_tile ? a->win_max_seg : win ? a->win_total_qblocks : a->total_qblocks, H, H, hd, scale,
+                         one_tile ? 8 : win ? 0 : a->uniform_segments ? 2 : 0, stream));
     TRY(vlm_gemm_bf16(a->attn, w.wproj, w.bproj, a->x, a->x, N, E, E, E, E, E, E, VLM_EPI_BIAS | VLM_EPI_RESIDUAL, stream));
-    TRY(vlm_layernorm(a->x, w.ln2_w, w.ln2_b, a->xn, N, E, c.ln_eps, stream));
-    TRY(vlm_gemm_bf16(a->xn, w.wfc1, w.bfc1, nullptr, a->mlp, N, MH, E, E, E, MH, 0, VLM_EPI_BIAS | VLM_EPI_GELU_FAST, stream));
+    TRY(vit_norm(f, a->x, w.ln2_w, w.ln2_b, a->xn, N, E, c.ln_eps, stream));
+    TRY(vlm_gemm_bf16(a->xn, w.wfc1, w.bfc1, nullptr, a->mlp, N, f.fc1_rows * MH, E, E, E, MH, 0, VLM_EPI_BIAS | f.fc1_epi, stream));
     TRY(vlm_gemm_bf16(a->mlp, w.wfc2, w.bfc2, a->x, a->x, N, E, MH, MH, MH, E, E, VLM_EPI_BIAS | VLM_EPI_RESIDUAL, stream));
+    if (f.taps && w.tap_w0) {             // DeepStack tap -> tap_out[tap]
+      TRY(merger(w.tap_ln_w, w.tap_ln_b, Nm, EM, w.tap_w0, w.tap_b0, w.tap_w2, w.tap_b2,
+                 off(a->tap_out, (size_t)tap * Nm * c.out_dim * 2)));
+      ++tap;
+    }
   }
-  // PatchMerger: LN -> [N/4, 4E] -> Linear + GELU(erf) -> Linear
-  TRY(vlm_layernorm(a->x, v->g.ln_q_w, v->g.ln_q_b, a->xn, N, E, c.ln_eps, stream));
-  const int Nm = N / mm, EM = E * mm;
-  TRY(vlm_gemm_bf16(a->xn, v->g.wm0, v->g.bm0, nullptr, a->mrg, Nm, EM, EM, EM, EM, EM, 0, VLM_EPI_BIAS | VLM_EPI_GELU_ERF, stream));
-  TRY(vlm_gemm_bf16(a->mrg, v->g.wm2, v->g.bm2, nullptr, a->out, Nm, c.out_dim, EM, EM, EM, c.out_dim, 0, VLM_EPI_BIAS, stream));
+  // a windowed form's merger rows borrow the mlp workspace and go back out of window order
+  TRY(merger(v->g.ln_q_w, v->g.ln_q_b, N, E, v->g.wm0, v->g.bm0, v->g.wm2, v->g.bm2, f.windowed ? a->mlp : a->out));
+  if (f.windowed) TRY(vlm_embed_gather(a->reverse_index, a->mlp, a->out, Nm, c.out_dim, c.out_dim, Nm, stream));
   return 0;
 }
 

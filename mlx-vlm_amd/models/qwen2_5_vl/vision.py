@@ -1,7 +1,9 @@
 """Qwen2.5-VL vision tower on MI355X - host mirror of the reference's
 mlx_vlm/models/qwen2_5_vl/vision.py (VisionModel, same constructor / call / sanitize contract).
 
-The numerical work is one call into the native ViT engine in its Qwen2.5 form (csrc/engine.hip: patch GEMM -> gather into
+The host side the Qwen towers share (geometry, patch-weight fold, q / k interleave, rotary and per-frame tables, workspaces,
+the engine call) is qwen2_vl.vision.VisionTower; this file adds the family's tensors, flag word and window tables.  The numerical
+work is one call into the native ViT engine, vlm_vit_forward with the Qwen2.5 facts (csrc/engine.hip: patch GEMM -> gather into
 window order -> depth x [RMSNorm, qkv GEMM + bias + 2-D rope, window or full attention, proj GEMM + bias + residual, RMSNorm,
 gate/up GEMM + bias + SwiGLU, down GEMM + bias + residual] -> PatchMerger -> gather back).  The host prepares integer tables
 from `grid_thw`, which the reference also does on the host with .tolist() (vision.py:228,269,340-346): the window index, the
@@ -9,7 +11,6 @@ window table, the rotary rows in window order, the full-image cu_seqlens and the
 """
 from __future__ import annotations
 
-import ctypes as C
 import os
 from typing import Dict, Optional
 
@@ -17,8 +18,7 @@ import numpy as np
 import torch
 
 from ... import _lib
-from ..._lib import check
-from ..qwen2_vl.vision import check_array_shape, rot_pos_ids
+from ..qwen2_vl.vision import VisionTower, full_cu_seqlens, rot_pos_ids
 from .config import VisionConfig
 
 ONE_TILE_MAX = 64          # tokens of the one-tile attention kernel (csrc/attn_window.hip)
@@ -63,14 +63,6 @@ def dedup_cu(cu) -> np.ndarray:
     return np.asarray(out, dtype=np.int32)
 
 
-def full_cu_seqlens(grid_thw) -> np.ndarray:
-    """reference vision.py:360-373: one segment per frame"""
-    lens = []
-    for t, h, w in np.asarray(grid_thw).tolist():
-        lens += [h * w] * t
-    return np.concatenate([[0], np.cumsum(lens)]).astype(np.int32)
-
-
 def host_tables(grid_thw, window_size: int, spatial_merge_size: int, patch_size: int):
     """-> dict of numpy tables: window_index, cu_window (zero-length windows dropped), reverse_index, cu_full, pos (the
     (h, w) rotary position ids [N, 2] in WINDOW order)."""
@@ -97,99 +89,45 @@ def pad_mlp(wg, bg, wu, bu, wd, pad_to: int = MLP_PAD):
     return wgu, bgu, wdp, ip
 
 
-class VisionModel:
+class VisionModel(VisionTower):
     def __init__(self, config: VisionConfig, device="cuda"):
-        self.config = config
-        self.model_type = config.model_type
-        if self.model_type != "qwen2_5_vl":
-            raise ValueError(f"Unsupported model type: {self.model_type}")
-        self.spatial_merge_size = config.spatial_merge_size
+        if config.model_type != "qwen2_5_vl":
+            raise ValueError(f"Unsupported model type: {config.model_type}")
+        super().__init__(config, device, config.hidden_size, config.out_hidden_size,
+                         (config.intermediate_size + MLP_PAD - 1) // MLP_PAD * MLP_PAD)
         self.spatial_merge_unit = config.spatial_merge_size ** 2
         self.window_size = config.window_size
         self.patch_size = config.patch_size
         self.fullatt_block_indexes = list(config.fullatt_block_indexes)
-        self.device = device
-        self.embed_dim = config.hidden_size
-        self.num_heads = config.num_heads
-        self.head_dim = config.hidden_size // config.num_heads
-        self.patch_dim = config.in_channels * config.temporal_patch_size * config.patch_size * config.patch_size
-        self.patch_k = (self.patch_dim + 63) // 64 * 64          # K of the patch GEMM, zero padded
-        self.mlp_hidden = (config.intermediate_size + MLP_PAD - 1) // MLP_PAD * MLP_PAD
-        self._handle = None
-        self._w: Dict[str, torch.Tensor] = {}
-        self._tab_cache: Dict[tuple, tuple] = {}
-
-    # ------------------------------------------------------------------ weights
-    @property
-    def dtype(self):
-        return torch.bfloat16
 
     def load_weights(self, W: Dict[str, torch.Tensor]):
         """W: sanitized names relative to the tower (`patch_embed.proj.weight`, `blocks.i....`, `merger....`)."""
-        c, dev = self.config, self.device
+        c, keep = self.config, self._keep
         if self.head_dim != 80:
             raise NotImplementedError(f"vision head_dim = {self.head_dim}: the Qwen2.5-VL tower is built for head_dim 80 "
                                       "(hidden_size 1280 / 16 heads)")
         if c.depth > 64 or any(i < 0 or i >= c.depth for i in self.fullatt_block_indexes):
             raise NotImplementedError(f"depth = {c.depth}, fullatt_block_indexes = {self.fullatt_block_indexes}: up to 64 blocks")
-        L = _lib.lib()
-        bf = torch.bfloat16
-
-        def keep(name, t):
-            t = t.to(device=dev, dtype=bf).contiguous()
-            self._w[name] = t
-            return t
-
-        pw = W["patch_embed.proj.weight"]
-        if pw.dim() == 5:
-            # (O, T, H, W, C) channels-last after sanitize -> columns in the processor's (C, T, ph, pw) order (as Qwen2-VL)
-            pw = pw.permute(0, 4, 1, 2, 3).reshape(pw.shape[0], -1)
-        wp = torch.zeros(c.hidden_size, self.patch_k, dtype=bf, device=dev)
-        wp[:, : self.patch_dim] = pw.to(device=dev, dtype=bf)
-        self._w["patch"] = wp
-
-        E, hd, half = c.hidden_size, self.head_dim, self.head_dim // 2
-        cfg = _lib.VitConfig(c.depth, E, c.num_heads, self.mlp_hidden, self.patch_k, c.spatial_merge_size, c.out_hidden_size,
-                             1e-6, _lib.VIT_QK_INTERLEAVED | _lib.VIT_FORM_QWEN2_5)   # nn.RMSNorm(eps=1e-6): vision.py:110,180-181
-        # q / k rows interleaved per head for the rope-in-epilogue GEMM: (d, d + hd/2) -> (2d, 2d + 1), as Qwen2-VL does
-        inter = torch.stack([torch.arange(half), torch.arange(half) + half], dim=1).reshape(-1)
-        perm = (torch.arange(2 * c.num_heads)[:, None] * hd + inter[None, :]).reshape(-1)
-        qk_perm = torch.cat([perm, torch.arange(2 * E, 3 * E)])
-        h = C.c_void_p()
-        check(L.vlm_vit_create(C.byref(cfg), C.byref(h)), "vit_create")
-        self._handle = h
+        wp = self._patch_weight(W)
+        self._create(_lib.VIT_QK_INTERLEAVED | _lib.VIT_FORM_QWEN2_5)
+        perm = self.qk_perm()
         for i in range(c.depth):
             p = f"blocks.{i}."
             wgu, bgu, wd, ip = pad_mlp(W[p + "mlp.gate_proj.weight"], W[p + "mlp.gate_proj.bias"], W[p + "mlp.up_proj.weight"],
                                        W[p + "mlp.up_proj.bias"], W[p + "mlp.down_proj.weight"])
             assert ip == self.mlp_hidden
-            ptr = {
-                "ln1_w": keep(p + "norm1.weight", W[p + "norm1.weight"]),
-                "wqkv": keep(p + "attn.qkv.weight", W[p + "attn.qkv.weight"][qk_perm.to(W[p + "attn.qkv.weight"].device)]),
-                "bqkv": keep(p + "attn.qkv.bias", W[p + "attn.qkv.bias"][qk_perm.to(W[p + "attn.qkv.bias"].device)]),
-                "wproj": keep(p + "attn.proj.weight", W[p + "attn.proj.weight"]),
-                "bproj": keep(p + "attn.proj.bias", W[p + "attn.proj.bias"]),
-                "ln2_w": keep(p + "norm2.weight", W[p + "norm2.weight"]),
-                "wfc1": keep(p + "mlp.gate_up.weight", wgu), "bfc1": keep(p + "mlp.gate_up.bias", bgu),
-                "wfc2": keep(p + "mlp.down_proj.weight", wd), "bfc2": keep(p + "mlp.down_proj.bias", W[p + "mlp.down_proj.bias"]),
-            }
-            blk = _lib.VitBlock(ptr["ln1_w"].data_ptr(), None, ptr["wqkv"].data_ptr(), ptr["bqkv"].data_ptr(),
-                                ptr["wproj"].data_ptr(), ptr["bproj"].data_ptr(), ptr["ln2_w"].data_ptr(), None,
-                                ptr["wfc1"].data_ptr(), ptr["bfc1"].data_ptr(), ptr["wfc2"].data_ptr(), ptr["bfc2"].data_ptr())
-            check(L.vlm_vit_set_block(h, i, C.byref(blk)), "vit_set_block")
+            wqkv, bqkv = W[p + "attn.qkv.weight"], W[p + "attn.qkv.bias"]
+            self._set_block(i, [
+                keep(p + "norm1.weight", W[p + "norm1.weight"]), None,
+                keep(p + "attn.qkv.weight", wqkv[perm.to(wqkv.device)]), keep(p + "attn.qkv.bias", bqkv[perm.to(bqkv.device)]),
+                keep(p + "attn.proj.weight", W[p + "attn.proj.weight"]), keep(p + "attn.proj.bias", W[p + "attn.proj.bias"]),
+                keep(p + "norm2.weight", W[p + "norm2.weight"]), None,
+                keep(p + "mlp.gate_up.weight", wgu), keep(p + "mlp.gate_up.bias", bgu),
+                keep(p + "mlp.down_proj.weight", wd), keep(p + "mlp.down_proj.bias", W[p + "mlp.down_proj.bias"])])
         m = {n: keep("merger." + n, W["merger." + n]) for n in ("ln_q.weight", "mlp.0.weight", "mlp.0.bias", "mlp.2.weight",
                                                                  "mlp.2.bias")}
-        gl = _lib.VitGlobals(wp.data_ptr(), m["ln_q.weight"].data_ptr(), None, m["mlp.0.weight"].data_ptr(),
-                             m["mlp.0.bias"].data_ptr(), m["mlp.2.weight"].data_ptr(), m["mlp.2.bias"].data_ptr())
-        check(L.vlm_vit_set_globals(h, C.byref(gl)), "vit_set_globals")
+        self._set_globals([wp, m["ln_q.weight"], None, m["mlp.0.weight"], m["mlp.0.bias"], m["mlp.2.weight"], m["mlp.2.bias"]])
         self._fullatt_mask = sum(1 << i for i in set(self.fullatt_block_indexes))
-
-    def __del__(self):
-        try:
-            if self._handle is not None:
-                _lib.lib().vlm_vit_destroy(self._handle)
-        except Exception:
-            pass
 
     # ------------------------------------------------------------------ host tables
     def get_window_index(self, grid_thw):
@@ -197,37 +135,16 @@ class VisionModel:
         wi, cu = get_window_index(grid_thw, self.window_size, self.spatial_merge_size, self.patch_size)
         return wi, np.asarray(cu, dtype=np.int64)
 
-    def rot_pos_emb(self, grid_thw, pos=None) -> torch.Tensor:
-        """freqs [N, head_dim/2] fp32 (reference vision.py:225-259); pos: position ids in another row order"""
-        g = np.asarray(grid_thw)
-        if pos is None:
-            pos = rot_pos_ids(g, self.spatial_merge_size)
-        dim = self.head_dim // 2
-        inv_freq = 1.0 / (10000.0 ** (torch.arange(0, dim, 2, dtype=torch.float32) / dim))
-        seq = torch.arange(int(g[:, 1:].max()), dtype=torch.float32)
-        full = torch.outer(seq, inv_freq)
-        return full[torch.from_numpy(pos)].reshape(pos.shape[0], -1)
-
-    def _tables(self, grid_thw):
-        key = tuple(map(tuple, np.asarray(grid_thw).tolist()))
-        hit = self._tab_cache.get(key)
-        if hit is None:
-            t = host_tables(grid_thw, self.window_size, self.spatial_merge_size, self.patch_size)
-            freqs = self.rot_pos_emb(grid_thw, t["pos"])                                        # rows in window order
-            cs = _lib.h2d(torch.stack([torch.cos(freqs), torch.sin(freqs)]).contiguous(), self.device)   # ONE table
-            full_lens, win_lens = np.diff(t["cu_full"]), np.diff(t["cu_window"])
-            hit = {
-                "cos": cs[0], "sin": cs[1], "cs": cs,
-                "cu_full": _lib.h2d(t["cu_full"], self.device), "nseg": len(full_lens),
-                "nqb": int(sum((int(l) + 127) // 128 for l in full_lens)), "uniform": int(len(set(full_lens.tolist())) == 1),
-                "cu_win": _lib.h2d(t["cu_window"], self.device), "win_nseg": len(win_lens),
-                "win_nqb": int(sum((int(l) + 127) // 128 for l in win_lens)), "win_max": int(win_lens.max()),
-                "window_index": _lib.h2d(t["window_index"].astype(np.int32), self.device),
-                "reverse_index": _lib.h2d(t["reverse_index"].astype(np.int32), self.device),
-            }
-            if len(self._tab_cache) > 64:
-                self._tab_cache.clear()
-            self._tab_cache[key] = hit
+    def _make_tables(self, grid_thw) -> dict:
+        t = host_tables(grid_thw, self.window_size, self.spatial_merge_size, self.patch_size)
+        hit = super()._make_tables(grid_thw, t["pos"])                                          # rotary rows in window order
+        win_lens = np.diff(t["cu_window"])
+        hit.update({
+            "cu_win": _lib.h2d(t["cu_window"], self.device), "win_nseg": len(win_lens),
+            "win_nqb": int(sum((int(n) + 127) // 128 for n in win_lens)), "win_max": int(win_lens.max()),
+            "window_index": _lib.h2d(t["window_index"].astype(np.int32), self.device),
+            "reverse_index": _lib.h2d(t["reverse_index"].astype(np.int32), self.device),
+        })
         return hit
 
     def one_tile(self, win_max: int) -> bool:
@@ -241,42 +158,9 @@ class VisionModel:
     def __call__(self, hidden_states: torch.Tensor, grid_thw, output_hidden_states: Optional[bool] = None):
         """hidden_states: pixel_values [N, C*T*ph*pw] (f32 or bf16, rows as the processor emits them).
         -> [N / merge^2, out_hidden_size] bf16, rows in the processor's order."""
-        from ... import ops
-
-        c = self.config
-        if not hidden_states.is_cuda:
-            hidden_states = _lib.h2d(hidden_states, self.device)
-        N = hidden_states.shape[0]
-        if hidden_states.dtype != torch.float32:
-            hidden_states = hidden_states.to(torch.float32)          # bf16 -> fp32 -> bf16 is lossless
-        x = ops.cast_pad(hidden_states.contiguous(), self.patch_k)
+        x = self._patch_rows(hidden_states)
         t = self._tables(grid_thw)
-        E, dev = c.hidden_size, self.device
-        mm = self.spatial_merge_unit
-        bf = torch.bfloat16
-        ws = {n: torch.empty(N, d, dtype=bf, device=dev) for n, d in
-              (("x", E), ("xn", E), ("qkv", 3 * E), ("attn", E), ("mlp", self.mlp_hidden))}
-        mrg = torch.empty(N // mm, E * mm, dtype=bf, device=dev)
-        out = torch.empty(N // mm, c.out_hidden_size, dtype=bf, device=dev)
-        a = _lib.VitArgs(x.data_ptr(), N, t["cos"].data_ptr(), t["sin"].data_ptr(), t["cu_full"].data_ptr(), t["nseg"], t["nqb"],
-                         ws["x"].data_ptr(), ws["xn"].data_ptr(), ws["qkv"].data_ptr(), ws["attn"].data_ptr(),
-                         ws["mlp"].data_ptr(), mrg.data_ptr(), out.data_ptr(), t["uniform"],
-                         t["cu_win"].data_ptr(), t["win_nseg"], t["win_nqb"], t["win_max"], int(self.one_tile(t["win_max"])),
-                         t["window_index"].data_ptr(), t["reverse_index"].data_ptr(), self._fullatt_mask)
-        check(_lib.lib().vlm_vit_forward(self._handle, C.byref(a), C.c_void_p(torch.cuda.current_stream().cuda_stream)),
-              "vit_forward")
-        return out
-
-    # ------------------------------------------------------------------ checkpoint key/layout fixups
-    def sanitize(self, weights):
-        """reference vision.py:395-413."""
-        out = {}
-        for k, v in weights.items():
-            if "position_ids" in k:
-                continue
-            if "patch_embed.proj.weight" in k:
-                out[k] = v if check_array_shape(v) else v.permute(0, 2, 3, 4, 1)
-            else:
-                out[k] = v
-        return out
-
+        return self._forward(x, t, win_cu_seqlens=t["cu_win"].data_ptr(), win_nseg=t["win_nseg"], win_total_qblocks=t["win_nqb"],
+                             win_max_seg=t["win_max"], win_one_tile=int(self.one_tile(t["win_max"])),
+                             window_index=t["window_index"].data_ptr(), reverse_index=t["reverse_index"].data_ptr(),
+                             fullatt_mask=self._fullatt_mask)
