@@ -49,6 +49,12 @@ extern "C" {
  * 0.5 x (1 + tanh(sqrt(2/pi) (x + 0.044715 x^3))) on the bf16-rounded acc + bias, every elementary op rounded to bf16 as
  * the two GELU forms above (qwen3_vl/vision.py:169).  Every tile, staging and split-K form that takes VLM_EPI_GELU_FAST. */
 #define VLM_EPI_GELU_TANH 256
+/* vlm_gemm_bf16 only, added within ABI v8: layer scale, x = x + ls * f(x) (internvl_chat/vision.py:126-132).  Valid only as
+ * VLM_EPI_BIAS | VLM_EPI_RESIDUAL | VLM_EPI_LAYERSCALE.  `bias` then points at bf16 [2][N], contiguous: row 0 the bias, row 1
+ * the per-column scale ls.  C[m][n] = T(res[m][n] + T(T(acc + bias[n]) * ls[n])), T = one rounding to bf16 - the three
+ * roundings of the reference's typed graph (Linear, multiply, add).  Every tile, staging and split-K form that takes
+ * VLM_EPI_BIAS | VLM_EPI_RESIDUAL; res may be C.  vlm_encoder_forward takes the bit in act_epilogue (below). */
+#define VLM_EPI_LAYERSCALE 512
 
 int vlm_abi_version(void);
 
@@ -762,8 +768,11 @@ int vlm_llm_get_tuning(void* handle, int key);
  * residual, LayerNorm, fc1 GEMM + bias + activation, fc2 GEMM + bias + residual] enqueued back to back.
  * x [N][E] residual stream (in / out); workspaces xn [N][E], qkv [N][3 H head_dim], attn [N][H head_dim], mlp [N][MH];
  * wqkv rows [q | k | v] of H * head_dim each (head_dim = the kernel's width: 64 / 80 / 128 - narrower heads zero-padded
- * by the caller, wo's columns likewise); act_epilogue VLM_EPI_GELU_FAST / VLM_EPI_GELU_ERF / 0; cu_seqlens int32
- * [nseg + 1], total_qblocks = sum ceil(len / 128); uniform_segments: vlm_attn_prefill's placement hint. */
+ * by the caller, wo's columns likewise); act_epilogue VLM_EPI_GELU_FAST / VLM_EPI_GELU_ERF / VLM_EPI_GELU_TANH / 0; cu_seqlens int32
+ * [nseg + 1], total_qblocks = sum ceil(len / 128); uniform_segments: vlm_attn_prefill's placement hint.
+ * Added within ABI v8: act_epilogue | VLM_EPI_LAYERSCALE - the InternViT layer (internvl_chat/vision.py:126-132),
+ * x = x + ls1 * out_proj(..); x = x + ls2 * fc2(..): bo and b2 then point at bf16 [2][E], the bias row followed by the
+ * ls1 / ls2 row, and both GEMMs run VLM_EPI_BIAS | VLM_EPI_RESIDUAL | VLM_EPI_LAYERSCALE.  Without the bit nothing changes. */
 typedef struct vlm_enc_layer {
   const void *ln1_w, *ln1_b, *wqkv, *bqkv, *wo, *bo, *ln2_w, *ln2_b, *w1, *b1, *w2, *b2;
 } vlm_enc_layer;

@@ -882,7 +882,11 @@ extern "C" int vlm_encoder_forward(const vlm_enc_layer* layers, int n_layers, vo
   if (!layers || n_layers < 0 || !x || !xn || !qkv || !attn || !mlp || !cu_seqlens || N <= 0 || E <= 0 || H <= 0 || head_dim <= 0 ||
       MH <= 0)
     return 1;
-  if (act_epilogue != VLM_EPI_GELU_FAST && act_epilogue != VLM_EPI_GELU_ERF && act_epilogue != 0) return 1;
+  // VLM_EPI_LAYERSCALE in act_epilogue: bo / b2 are [2][E] (bias row, scale row) and the wo / w2 GEMMs scale before the residual
+  const int res_epi = VLM_EPI_BIAS | VLM_EPI_RESIDUAL | (act_epilogue & VLM_EPI_LAYERSCALE);
+  act_epilogue &= ~VLM_EPI_LAYERSCALE;
+  if (act_epilogue != VLM_EPI_GELU_FAST && act_epilogue != VLM_EPI_GELU_ERF && act_epilogue != VLM_EPI_GELU_TANH && act_epilogue != 0)
+    return 1;
   const int HD = H * head_dim;                       // (padded) attention width: qkv rows are [q | k | v] of HD columns each
   for (int i = 0; i < n_layers; ++i) {
     const vlm_enc_layer& w = layers[i];
@@ -890,10 +894,10 @@ extern "C" int vlm_encoder_forward(const vlm_enc_layer* layers, int n_layers, vo
     TRY(vlm_gemm_bf16(xn, w.wqkv, w.bqkv, nullptr, qkv, N, 3 * HD, E, E, E, 3 * HD, 0, VLM_EPI_BIAS, stream));
     TRY(vlm_attn_prefill(qkv, off(qkv, (size_t)HD * 2), off(qkv, (size_t)2 * HD * 2), attn, 3 * HD, 3 * HD, 3 * HD, HD, cu_seqlens,
                          nseg, total_qblocks, H, H, head_dim, scale, uniform_segments ? 2 : 0, stream));
-    TRY(vlm_gemm_bf16(attn, w.wo, w.bo, x, x, N, E, HD, HD, HD, E, E, VLM_EPI_BIAS | VLM_EPI_RESIDUAL, stream));
+    TRY(vlm_gemm_bf16(attn, w.wo, w.bo, x, x, N, E, HD, HD, HD, E, E, res_epi, stream));
     TRY(vlm_layernorm(x, w.ln2_w, w.ln2_b, xn, N, E, ln_eps, stream));
     TRY(vlm_gemm_bf16(xn, w.w1, w.b1, nullptr, mlp, N, MH, E, E, E, MH, 0, VLM_EPI_BIAS | act_epilogue, stream));
-    TRY(vlm_gemm_bf16(mlp, w.w2, w.b2, x, x, N, E, MH, MH, MH, E, E, VLM_EPI_BIAS | VLM_EPI_RESIDUAL, stream));
+    TRY(vlm_gemm_bf16(mlp, w.w2, w.b2, x, x, N, E, MH, MH, MH, E, E, res_epi, stream));
   }
   return 0;
 }

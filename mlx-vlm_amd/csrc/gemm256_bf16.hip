@@ -116,6 +116,10 @@ __device__ __forceinline__ void epilogue256(f32x4_t (&acc)[8][NF], char* smem, c
 #pragma unroll
         for (int r = 0; r < 4; ++r) v[r] = gelu_tanh_(rbf(v[r]));
       }
+      if (EPI & VLM_EPI_LAYERSCALE) {      // T(T(acc + bias) * ls[n]): the scale row follows the bias row (gemm_bf16.hip)
+        const uint2 g = *reinterpret_cast<const uint2*>(bias + N + n);
+        v[0] = rbf(v[0]) * bf_lo(g.x); v[1] = rbf(v[1]) * bf_hi(g.x); v[2] = rbf(v[2]) * bf_lo(g.y); v[3] = rbf(v[3]) * bf_hi(g.y);
+      }
       uint2 o;
       o.x = pack_bf2(v[0], v[1]);
       o.y = pack_bf2(v[2], v[3]);
@@ -542,6 +546,10 @@ __global__ __launch_bounds__(512) void gemm256p_kernel(const bf16_t* __restrict_
 #pragma unroll
           for (int r = 0; r < 4; ++r) v[r] = gelu_tanh_(rbf(v[r]));
         }
+        if (EPI & VLM_EPI_LAYERSCALE) {
+          const uint2 g = *reinterpret_cast<const uint2*>(bias + N + n);
+          v[0] = rbf(v[0]) * bf_lo(g.x); v[1] = rbf(v[1]) * bf_hi(g.x); v[2] = rbf(v[2]) * bf_lo(g.y); v[3] = rbf(v[3]) * bf_hi(g.y);
+        }
         uint2 o;
         o.x = pack_bf2(v[0], v[1]);
         o.y = pack_bf2(v[2], v[3]);
@@ -837,6 +845,8 @@ __attribute__((visibility("hidden"))) int vlm_gemm256_try(const void* A, const v
       return launch256<VLM_EPI_BIAS | VLM_EPI_GELU_TANH>(A, W, bias, res, C, M, N, K, lda, ldw, ldc, ldres, st);
     case VLM_EPI_BIAS | VLM_EPI_RESIDUAL:
       return launch256<VLM_EPI_BIAS | VLM_EPI_RESIDUAL>(A, W, bias, res, C, M, N, K, lda, ldw, ldc, ldres, st);
+    case VLM_EPI_BIAS | VLM_EPI_RESIDUAL | VLM_EPI_LAYERSCALE:
+      return launch256<VLM_EPI_BIAS | VLM_EPI_RESIDUAL | VLM_EPI_LAYERSCALE>(A, W, bias, res, C, M, N, K, lda, ldw, ldc, ldres, st);
     case VLM_EPI_RESIDUAL: return launch256<VLM_EPI_RESIDUAL>(A, W, bias, res, C, M, N, K, lda, ldw, ldc, ldres, st);
     case VLM_EPI_SWIGLU:
       if (N % 16 != 0) return -1;

@@ -321,6 +321,11 @@ __global__ __launch_bounds__(256) void gemm_bf16_kernel(const bf16_t* __restrict
 #pragma unroll
           for (int r = 0; r < 4; ++r) v[r] = gelu_tanh_(rbf(v[r]));
         }
+        if (EPI & VLM_EPI_LAYERSCALE) {
+          // layer scale (internvl_chat/vision.py:126-132): T(T(acc + bias) * ls[n]); the scale row follows the bias row
+          const uint2 g = *reinterpret_cast<const uint2*>(bias + N + n);
+          v[0] = rbf(v[0]) * bf_lo(g.x); v[1] = rbf(v[1]) * bf_hi(g.x); v[2] = rbf(v[2]) * bf_lo(g.y); v[3] = rbf(v[3]) * bf_hi(g.y);
+        }
         uint2 o;
         o.x = pack_bf2(v[0], v[1]);
         o.y = pack_bf2(v[2], v[3]);
@@ -382,6 +387,12 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restr
   if (EPI & VLM_EPI_GELU_TANH) {
 #pragma unroll
     for (int r = 0; r < 8; ++r) v[r] = gelu_tanh_(rbf(v[r]));
+  }
+  if (EPI & VLM_EPI_LAYERSCALE) {
+    const uint4 g = *reinterpret_cast<const uint4*>(bias + N + n);
+    const float gs[8] = {bf_lo(g.x), bf_hi(g.x), bf_lo(g.y), bf_hi(g.y), bf_lo(g.z), bf_hi(g.z), bf_lo(g.w), bf_hi(g.w)};
+#pragma unroll
+    for (int r = 0; r < 8; ++r) v[r] = rbf(v[r]) * gs[r];
   }
   uint4 u;
   u.x = pack_bf2(v[0], v[1]); u.y = pack_bf2(v[2], v[3]); u.z = pack_bf2(v[4], v[5]); u.w = pack_bf2(v[6], v[7]);
@@ -596,7 +607,7 @@ template <int EPI>
 void launch_reduce(const float* ws, int splits, const void* bias, const void* res, void* C, int M, int N, int ldc, int ldres,
                    hipStream_t st) {
   const VlmGemmTail* t = t_tail;
-  if (t && !(EPI & (VLM_EPI_GELU_FAST | VLM_EPI_GELU_ERF | VLM_EPI_GELU_TANH | VLM_EPI_SWIGLU | VLM_EPI_ROPE2D))) {
+  if (t && !(EPI & (VLM_EPI_GELU_FAST | VLM_EPI_GELU_ERF | VLM_EPI_GELU_TANH | VLM_EPI_SWIGLU | VLM_EPI_ROPE2D | VLM_EPI_LAYERSCALE))) {
     if (t->kind == VLM_TAIL_RMSNORM && N <= 4096 && t->norm_w && t->xn && t->ldxn % 8 == 0) {
       hipLaunchKernelGGL((splitk_reduce_norm_kernel<EPI>), dim3(M), dim3(256), (size_t)N * 2, st, ws, splits, (const bf16_t*)bias,
                          (const bf16_t*)res, (bf16_t*)C, M, N, ldc, ldres, (const bf16_t*)t->norm_w, t->eps, (bf16_t*)t->xn, t->ldxn);
@@ -870,7 +881,7 @@ static int gemm_dispatch(const void* A, const void* W, const void* bias, const v
 
 extern "C" int vlm_gemm_bf16(const void* A, const void* W, const void* bias, const void* res, void* C, int M, int N,
                              int K, int lda, int ldw, int ldc, int ldres, int epilogue, void* stream) {
-  if (epilogue & ~(VLM_EPI_BIAS | VLM_EPI_GELU_FAST | VLM_EPI_GELU_ERF | VLM_EPI_GELU_TANH | VLM_EPI_RESIDUAL | VLM_EPI_SWIGLU)) return VLM_ERR_ARG;
+  if (epilogue & ~(VLM_EPI_BIAS | VLM_EPI_GELU_FAST | VLM_EPI_GELU_ERF | VLM_EPI_GELU_TANH | VLM_EPI_RESIDUAL | VLM_EPI_SWIGLU | VLM_EPI_LAYERSCALE)) return VLM_ERR_ARG;
   return gemm_dispatch(A, W, bias, res, C, M, N, K, lda, ldw, ldc, ldres, epilogue, stream);
 }
 
@@ -914,6 +925,7 @@ static int gemm_dispatch(const void* A, const void* W, const void* bias, const v
     case VLM_EPI_BIAS | VLM_EPI_GELU_ERF: GO(VLM_EPI_BIAS | VLM_EPI_GELU_ERF);
     case VLM_EPI_BIAS | VLM_EPI_GELU_TANH: GO(VLM_EPI_BIAS | VLM_EPI_GELU_TANH);
     case VLM_EPI_BIAS | VLM_EPI_RESIDUAL: GO(VLM_EPI_BIAS | VLM_EPI_RESIDUAL);
+    case VLM_EPI_BIAS | VLM_EPI_RESIDUAL | VLM_EPI_LAYERSCALE: GO(VLM_EPI_BIAS | VLM_EPI_RESIDUAL | VLM_EPI_LAYERSCALE);      // bias = [2][N]: bias row, scale row
     case VLM_EPI_RESIDUAL: GO(VLM_EPI_RESIDUAL);
     case VLM_EPI_SWIGLU: GO(VLM_EPI_SWIGLU);
     case VLM_EPI_BIAS | VLM_EPI_SWIGLU: GO(VLM_EPI_BIAS | VLM_EPI_SWIGLU);      // bias interleaved like the (gate, up) rows

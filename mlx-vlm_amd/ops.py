@@ -16,6 +16,12 @@ from ._lib import check
 
 EPI_NONE, EPI_BIAS, EPI_GELU_FAST, EPI_GELU_ERF, EPI_RESIDUAL, EPI_SWIGLU = 0, 1, 2, 4, 8, 16
 EPI_GELU_TANH = 256                     # nn.GELU(approx="tanh") (the Qwen3-VL tower's MLP); gemm only
+EPI_LAYERSCALE = 512                    # x + ls * f(x) (the InternViT layer); gemm only, with EPI_BIAS | EPI_RESIDUAL: bias is [2, N]
+
+
+def bias_scale(bias, ls):
+    """the [2, N] operand of EPI_LAYERSCALE: the bias row, then the per-column scale row"""
+    return torch.stack([bias.reshape(-1), ls.reshape(-1)]).to(torch.bfloat16).contiguous()
 
 
 def _p(t: Optional[torch.Tensor]):

@@ -4,6 +4,7 @@
 
     qwen2_vl, idefics2            content = [text item, image items ...]            (LIST_WITH_IMAGE)
     qwen2_5_vl, qwen3_vl          content = [image items ..., text item]            (LIST_WITH_IMAGE_FIRST)
+    internvl_chat                 the same; an assistant message's content is the bare string (LIST_WITH_IMAGE_TYPE)
     llava-qwen2 / bunny-llama     content = "<image>\\n" * n + prompt, one image     (IMAGE_TOKEN_NEWLINE, single-image models)
     phi3_v                        content = "<|image_1|><|image_2|>..." + prompt    (NUMBERED_IMAGE_TOKENS)
     anything else                 plain text messages
@@ -19,7 +20,7 @@ from typing import Any, Dict, List, Union
 # model_type -> (kind, token).  kind: "list" = typed content list ("list_first": image items in front of the text item),
 # "token" = marker text in front of the prompt, "numbered" = <|image_N|> markers
 _FORMATS = {"qwen2_vl": ("list", None), "idefics2": ("list", None), "qwen2_5_vl": ("list_first", None),
-            "qwen3_vl": ("list_first", None),
+            "qwen3_vl": ("list_first", None), "internvl_chat": ("list_first_type", None),
             "llava-qwen2": ("token", "<image>\n"), "bunny-llama": ("token", "<image>\n"),
             "phi3_v": ("numbered", None)}
 _SINGLE_IMAGE_ONLY = {"llava-qwen2", "bunny-llama"}
@@ -89,11 +90,13 @@ def get_message_json(model_name: str, prompt: str, role: str = "user", skip_imag
         raise ValueError(f"Model {name} does not support multi-image chat. Please only use 1 image.")
     kind, token = _FORMATS[name]
     with_images = role == "user" and not skip_image_token and num_images > 0
-    if kind in ("list", "list_first"):
+    if kind in ("list", "list_first", "list_first_type"):
         content: List[Dict[str, str]] = [{"type": "text", "text": prompt, "content": prompt}]
         if with_images:
             images = [{"type": "image"}] * num_images
-            content = images + content if kind == "list_first" else content + images
+            content = content + images if kind == "list" else images + content
+        if kind == "list_first_type" and role == "assistant":           # reference 451-454
+            return {"role": role, "content": prompt}
         return {"role": role, "content": content}
     if kind == "token":
         return {"role": role, "content": f"{token * num_images}{prompt}" if with_images else prompt}

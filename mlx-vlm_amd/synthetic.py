@@ -62,6 +62,77 @@ IDEFICS2_8B = dict(
 )
 
 
+# InternVL3 / InternVL3.5 (OpenGVLab/InternVL3-2B, -8B, InternVL3_5-8B: InternViT-300M-448px tower + pixel-shuffle mlp1 + Qwen2.5 /
+# Qwen3), public HF config values
+_INTERNVIT_300M = dict(model_type="intern_vit_6b", hidden_size=1024, num_attention_heads=16, patch_size=14, num_hidden_layers=24,
+                       intermediate_size=4096, image_size=448, num_channels=3, layer_norm_eps=1e-6, qkv_bias=True,
+                       qk_normalization=False, norm_type="layer_norm")
+INTERNVL3_2B = dict(
+    model_type="internvl_chat", downsample_ratio=0.5, image_token_index=151667, vision_config=_INTERNVIT_300M,
+    text_config=dict(model_type="qwen2", hidden_size=1536, num_hidden_layers=28, intermediate_size=8960, num_attention_heads=12,
+                     num_key_value_heads=2, rms_norm_eps=1e-6, vocab_size=151674, rope_theta=1000000.0, tie_word_embeddings=False,
+                     attention_bias=True),
+)
+INTERNVL3_8B = dict(
+    INTERNVL3_2B, text_config=dict(INTERNVL3_2B["text_config"], hidden_size=3584, intermediate_size=18944, num_attention_heads=28,
+                                   num_key_value_heads=4, vocab_size=151674),
+)
+INTERNVL3_5_8B = dict(
+    INTERNVL3_2B, image_token_index=151671,
+    text_config=dict(model_type="qwen3", hidden_size=4096, num_hidden_layers=36, intermediate_size=12288, num_attention_heads=32,
+                     num_key_value_heads=8, head_dim=128, rms_norm_eps=1e-6, vocab_size=151936, rope_theta=1000000.0,
+                     tie_word_embeddings=False, attention_bias=False),
+)
+# tiny forms of both (tests, smoke runs): a 56-px tile of 17 tokens, 2 decoder layers
+INTERNVL_TINY_QWEN2 = dict(
+    model_type="internvl_chat", downsample_ratio=0.5, image_token_index=1001, video_token_index=1002,
+    vision_config=dict(_INTERNVIT_300M, hidden_size=128, num_attention_heads=2, num_hidden_layers=2, intermediate_size=256, image_size=56),
+    text_config=dict(model_type="qwen2", hidden_size=256, num_hidden_layers=2, intermediate_size=512, num_attention_heads=4,
+                     num_key_value_heads=2, rms_norm_eps=1e-6, vocab_size=1024, rope_theta=1000000.0, tie_word_embeddings=False,
+                     attention_bias=True),
+)
+INTERNVL_TINY_QWEN3 = dict(
+    INTERNVL_TINY_QWEN2, text_config=dict(INTERNVL_TINY_QWEN2["text_config"], model_type="qwen3", head_dim=128, attention_bias=False),
+)
+
+
+def internvl_weight_shapes(cfg) -> Dict[str, tuple]:
+    """name -> shape for an internvl_chat ModelConfig under the checkpoint's names (patch weight (O, kH, kW, C))"""
+    t, v = cfg.text_config, cfg.vision_config
+    E, I, D = v.hidden_size, v.intermediate_size, t.hidden_size
+    hd = getattr(t, "head_dim", None) or D // t.num_attention_heads
+    M = E * round(1 / cfg.downsample_ratio) ** 2
+    V = "vision_model."
+    s: Dict[str, tuple] = {V + "embeddings.class_embedding": (1, 1, E),
+                           V + "embeddings.position_embedding": (1, (v.image_size // v.patch_size) ** 2 + 1, E),
+                           V + "embeddings.patch_embedding.weight": (E, v.patch_size, v.patch_size, v.num_channels),
+                           V + "embeddings.patch_embedding.bias": (E,)}
+    for i in range(v.num_hidden_layers):
+        p = f"{V}encoder.layers.{i}."
+        s.update({p + "norm1.weight": (E,), p + "norm1.bias": (E,), p + "norm2.weight": (E,), p + "norm2.bias": (E,),
+                  p + "attn.qkv.weight": (3 * E, E), p + "attn.qkv.bias": (3 * E,), p + "attn.proj.weight": (E, E),
+                  p + "attn.proj.bias": (E,), p + "mlp.fc1.weight": (I, E), p + "mlp.fc1.bias": (I,),
+                  p + "mlp.fc2.weight": (E, I), p + "mlp.fc2.bias": (E,), p + "ls1": (E,), p + "ls2": (E,)})
+    s.update({"mlp1.0.weight": (M,), "mlp1.0.bias": (M,), "mlp1.1.weight": (D, M), "mlp1.1.bias": (D,), "mlp1.3.weight": (D, D),
+              "mlp1.3.bias": (D,), "language_model.model.embed_tokens.weight": (t.vocab_size, D)})
+    for i in range(t.num_hidden_layers):
+        p = f"language_model.model.layers.{i}."
+        s.update({p + "input_layernorm.weight": (D,), p + "post_attention_layernorm.weight": (D,),
+                  p + "self_attn.q_proj.weight": (t.num_attention_heads * hd, D), p + "self_attn.k_proj.weight": (t.num_key_value_heads * hd, D),
+                  p + "self_attn.v_proj.weight": (t.num_key_value_heads * hd, D), p + "self_attn.o_proj.weight": (D, t.num_attention_heads * hd),
+                  p + "mlp.gate_proj.weight": (t.intermediate_size, D), p + "mlp.up_proj.weight": (t.intermediate_size, D),
+                  p + "mlp.down_proj.weight": (D, t.intermediate_size)})
+        if t.attention_bias:
+            s.update({p + "self_attn.q_proj.bias": (t.num_attention_heads * hd,), p + "self_attn.k_proj.bias": (t.num_key_value_heads * hd,),
+                      p + "self_attn.v_proj.bias": (t.num_key_value_heads * hd,)})
+        else:
+            s.update({p + "self_attn.q_norm.weight": (hd,), p + "self_attn.k_norm.weight": (hd,)})
+    s["language_model.model.norm.weight"] = (D,)
+    if not t.tie_word_embeddings:
+        s["language_model.lm_head.weight"] = (t.vocab_size, D)
+    return s
+
+
 def idefics2_weight_shapes(cfg) -> Dict[str, tuple]:
     """name -> shape for an idefics2 ModelConfig, sanitized names (reference idefics2.py:294-321)"""
     t, v, p = cfg.text_config, cfg.vision_config, cfg.perceiver_config
@@ -174,6 +245,8 @@ def weight_shapes(cfg) -> Dict[str, tuple]:
         return phi3v_weight_shapes(cfg)
     if getattr(cfg, "model_type", None) == "idefics2":
         return idefics2_weight_shapes(cfg)
+    if getattr(cfg, "model_type", None) == "internvl_chat":
+        return internvl_weight_shapes(cfg)
     t, v = cfg.text_config, cfg.vision_config
     E, D = v.embed_dim, t.hidden_size
     hd = D // t.num_attention_heads
@@ -215,6 +288,10 @@ def random_weights(cfg, seed: int = 0, device="cuda", dtype=torch.bfloat16, std:
             W[name] = torch.empty(shape, dtype=dtype, device=device)
         elif name.endswith(("norm1.weight", "norm2.weight", "ln_q.weight", "layernorm.weight", "model.norm.weight",
                             "layrnorm.weight", "_norm.weight", ".norm.weight")):
+            W[name] = torch.ones(shape, dtype=dtype, device=device)
+        elif name.endswith((".ls1", ".ls2")):       # InternViT layer scale: 0.1 at initialisation, spread so that no two columns agree
+            W[name] = (0.05 + 0.1 * torch.rand(shape, generator=g, device=device, dtype=torch.float32)).to(dtype)
+        elif name == "mlp1.0.weight":
             W[name] = torch.ones(shape, dtype=dtype, device=device)
         elif name.endswith(".bias"):
             W[name] = torch.zeros(shape, dtype=dtype, device=device)

@@ -23,7 +23,7 @@ import torch
 # whole alias table is kept so that a lookup resolves exactly as it does there; families that are not built here then
 # fail in get_model_and_args with the reference's own "Model type ... not supported." (utils.py:633-635).
 # Built: qwen2_vl, qwen2_5_vl, qwen3_vl (dense; qwen3_vl_moe is refused), phi3_v, idefics2, llava_bunny (nanoLLaVA ships
-# `model_type: "llava-qwen2"`, Bunny `"bunny-llama"`).
+# `model_type: "llava-qwen2"`, Bunny `"bunny-llama"`), internvl_chat (InternVL3 / 3.5 with the InternViT-300M tower).
 MODEL_REMAPPING: Dict[str, str] = {
     "llava-qwen2": "llava_bunny", "bunny-llama": "llava_bunny", "llava_qwen2": "fastvlm", "lfm2-vl": "lfm2_vl",
     "cohere2_vision": "aya_vision", "jvlm": "jina_vlm", "phi4-siglip": "phi4_siglip", "sam3_video": "sam3",
@@ -227,6 +227,16 @@ def load_processor(model_path: str, config, image_preprocess: str = "host"):
                 pk["image_seq_len"] = pcfg["image_seq_len"]
             ipk.update({k: v for k, v in (pcfg.get("image_processor") or {}).items() if k in ("size",)})
         proc = Idefics2Processor(Idefics2ImageProcessor(**ipk), tok, chat_template=getattr(tok, "chat_template", None), **pk)
+        eos = config.eos_token_id if getattr(config, "eos_token_id", None) is not None else tok.eos_token_id
+        tok.stopping_criteria = StoppingCriteria(eos if isinstance(eos, list) else [eos], tok)
+        proc.detokenizer = _pick_detokenizer(model_path, tok)
+        return proc
+    if MODEL_REMAPPING.get(mt, mt) == "internvl_chat":
+        # reference internvl_chat/processor.py:394-461 (InternVLChatProcessor.from_pretrained): tokenizer + the dynamic-tiling
+        # image processor with the tile geometry of config.json / processor_config.json
+        from .models.internvl_chat import InternVLChatProcessor
+
+        proc = InternVLChatProcessor.from_pretrained(model_path, tokenizer=tok)
         eos = config.eos_token_id if getattr(config, "eos_token_id", None) is not None else tok.eos_token_id
         tok.stopping_criteria = StoppingCriteria(eos if isinstance(eos, list) else [eos], tok)
         proc.detokenizer = _pick_detokenizer(model_path, tok)
